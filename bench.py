@@ -9,9 +9,21 @@ dlog_sigma2, dKL) [+ flat-bucket gradient all-reduce and scalar KL all-reduce fo
                                                             torch.distributed.run, one rank per GPU, 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel =
-the bf16 complex MFMA GEMM, timed live with HIP events on the launch stream) and `cpu_baseline`
-(the numpy oracle on a bounded sample, rank 0, N = 1 only).
+Prints ONE JSON line on rank 0: `metric`, `value` (samples/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step`
+(wall time of the K timed steps / K), `step_ms`, `config`, `kl`.  A plain run does only that: set-up, warm-up, the K
+timed steps, the line.
+
+    --full                 everything else the benchmark measures, after the timed steps: `roofline` (dominant kernel =
+                           the bf16 complex MFMA GEMM, timed with HIP events in ten eager steps), `hbm_kernels_GBps`,
+                           and on rank 0 with N = 1 (unless --no-cpu-baseline) the other BASELINE configurations, the
+                           float32 full sizes, the data-parallel projection and `cpu_baseline` (the numpy oracle on a
+                           bounded sample).  With --graph off a --full run also brackets the timed launches with HIP events.
+    --dump-outputs DIR     after the timed steps, what the last timed step computed, as float32 DIR/<name>.npy (rank 0):
+                           y_real / y_imag (the layer's output), x_grad_real / x_grad_imag, grad_<parameter> for every
+                           parameter of the layer, kl.  Arrays of more than 2^20 elements are stored as the same fixed,
+                           seeded sample of 2^20 flat positions (about 28 MB in all at the default shape).  The inputs,
+                           the weights and the noise seed are fixed, so two builds run with the same arguments can be
+                           compared output for output.
 """
 import argparse
 import json
@@ -40,7 +52,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=BATCH, help="rows per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure what the headline figure does "
+                    "not need: roofline / HBM kernel figures and, with N = 1, the other configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to "
+                    "DIR/<name>.npy (float32; arrays above 2^20 elements as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: only the headline's own figures")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL over xGMI); gloo only for "
                     "functional tests of the N > 1 path on a single GPU (with --share-device)")
     ap.add_argument("--share-device", action="store_true", help="all ranks use cuda:0 (tests)")
@@ -463,6 +479,29 @@ def headline_check(B, dev):
         return {"passed": None, "error": f"{type(e).__name__}: {str(e)[:300]}"}
 
 
+DUMP_SAMPLE = 1 << 20
+
+
+def dump_outputs(out_dir, named):
+    """bench.py --dump-outputs: `named` = {name: tensor} of one step, written as float32 <out_dir>/<name>.npy; a tensor
+    of more than DUMP_SAMPLE elements is stored as the values at DUMP_SAMPLE flat positions drawn without replacement
+    by numpy's default_rng(0) (sorted), the same positions for every tensor of that size and in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    picks = {}
+    for name, t in named.items():
+        if t is None:
+            raise RuntimeError(f"bench.py --dump-outputs: the step produced no {name}")
+        a = t.detach()
+        n = a.numel()
+        if n > DUMP_SAMPLE:
+            if n not in picks:
+                idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+                picks[n] = torch.from_numpy(idx).to(a.device)
+            a = a.reshape(-1)[picks[n]]
+        np.save(os.path.join(out_dir, name + ".npy"), a.float().cpu().numpy())
+
+
 # The reference itself (PyTorch CPU path of ivannz/cplxmodule) cannot travel to the GPU box; its numbers are the ones taken
 # in the build container (BASELINE.md section 2, rows 2 / 2' / 2'' / 4): context beside `cpu_baseline`, never a target.
 REFERENCE_CPU = {
@@ -641,6 +680,55 @@ def _layout_key(prefix):
     return key
 
 
+def full_headline_figures(timer, graphed, grouped, B):
+    """bench.py --full: `roofline` and `hbm_kernels_GBps` of the headline step, from the HIP events `timer` took in the
+    eager steps after the timed region (or around the timed launches with --graph off) and, with N = 1, from replays of
+    the step's HBM kernels."""
+    launches, launch_frac = gemm_launch_table({k: timer.mean_ms(k) for k in timer.spans}, B, IN_F, OUT_F)
+    cg = [v for k, v in launches.items() if k.startswith("cgemm")]
+    gemm_ms = sum(cg) / len(cg) if cg else None
+    traffic, traffic_per = gemm_traffic() if B == BATCH else (None, None)
+    flops = 8.0 * B * IN_F * OUT_F          # algorithmic flop of ONE 4M complex GEMM launch
+    achieved = flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms else None
+    nw = IN_F * OUT_F
+
+    # the step's three HBM kernels: the calls the step made, re-issued ten times in a graph of their own (see replay_ms)
+    def replayed(key):
+        if grouped:                     # N > 1: other ranks are past this point; nothing extra beside their teardown
+            return timer.mean_ms(key)
+        try:
+            return timer.replay_ms(key)
+        except Exception as e:  # pragma: no cover - an auxiliary number must not take the line down
+            sys.stderr.write(f"bench.py: replay of {key} failed ({type(e).__name__}: {str(e)[:160]}); event spans instead\n")
+            return timer.mean_ms(key)
+
+    pk, rp_f, rp_b = (replayed(k) for k in ("prep_kl", "reparam_fwd", "reparam_bwd"))
+    nout = B * OUT_F
+    return {
+        "roofline": {"bound": "mfma", "kernel": "gemm_bf16_w4_kernel<CPLX> (4M complex GEMM, one wave per SIMD: fwd NN, dgrad NT + fused LRT term, wgrad TT + fused KL accumulate = 3 launches/step)",
+                     "achieved": round(achieved, 1) if achieved else None, "peak": BF16_PEAK_TFLOPS,
+                     "unit": "TFLOP/s", "frac": round(achieved / BF16_PEAK_TFLOPS, 4) if achieved else None,
+                     "traffic": traffic, "traffic_per_launch": traffic_per, "flop_per_launch": flops,
+                     "avg_launch_ms": round(gemm_ms, 4) if gemm_ms else None,
+                     # every GEMM launch of the step: forward NN, input gradient NT (with the LRT term 2 x ga fused into
+                     # its epilogue: counted with the GEMM's 8 B I O flop only), weight gradient TT; complex (8 B I O
+                     # flop) and the real variance GEMMs (2 B I O flop)
+                     "launch_ms": launches, "launch_frac": launch_frac,
+                     # the headline is a graph replay, inside which HIP events cannot be recorded
+                     "launch_ms_source": ("ten eager steps right after the timed region (same process, same kernels)"
+                                          if graphed else "the timed steps"),
+                     "traffic_source": "profiles/ PMC file of these kernels and shapes (bench.py: gemm_traffic), not this run"},
+        "hbm_kernels_GBps": {
+            # in-step: operand prep + KL sum + KL gradients in one pass (12 B read, 6 + 12 B written)
+            "prep_kl_fused(30B/elt)": round(30 * nw / (pk * 1e-3) / 1e9, 1) if pk else None,
+            "reparam_fwd(10B/out bf16, s2 bf16)": round(10 * nout / (rp_f * 1e-3) / 1e9, 1) if rp_f else None,
+            "reparam_bwd(8B/out bf16, s2 bf16)": round(8 * nout / (rp_b * 1e-3) / 1e9, 1) if rp_b else None,
+            "in_step_source": ("HIP events around the Python calls of ten eager steps (spans include allocation and launch gaps)"
+                               if grouped else "the step's own calls, ten per hipGraph replay (bench.py: KernelTimer.replay_ms)"),
+            "peak": HBM_PEAK_GBS},
+    }
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", 0))
@@ -681,14 +769,15 @@ def main():
     dp.FORCE_COLLECTIVES = bool(args.force_collectives)
 
     timer = KernelTimer()
-    timer.wrap(ops, "cgemm", _layout_key("cgemm"))       # forward NN, input gradient NT, weight gradient TT
-    timer.wrap(ops, "rgemm", _layout_key("rgemm"))
-    # the LRT input gradient: G conj(W) + 2 x ga in the epilogue of the persistent (N,T) kernel (one launch); when the
-    # kernel declines the shape the call runs cgemm (timed above as cgemm_NT) + the accumulate pass instead
-    timer.wrap(ops, "_cplx_lrt_dx", lambda g2r, *a, **k: "cgemm_NT_fused_dx" if g2r.dtype == torch.bfloat16 else None)
-    timer.wrap(ops, "prep_kl", lambda *a, **k: "prep_kl" if a[4] else None)
-    timer.wrap(ops, "reparam_fwd", lambda *a, **k: "reparam_fwd")
-    timer.wrap(ops, "reparam_bwd", lambda *a, **k: "reparam_bwd")
+    if args.full:                              # (the per-launch figures of `roofline` / `hbm_kernels_GBps`)
+        timer.wrap(ops, "cgemm", _layout_key("cgemm"))       # forward NN, input gradient NT, weight gradient TT
+        timer.wrap(ops, "rgemm", _layout_key("rgemm"))
+        # the LRT input gradient: G conj(W) + 2 x ga in the epilogue of the persistent (N,T) kernel (one launch); when the
+        # kernel declines the shape the call runs cgemm (timed above as cgemm_NT) + the accumulate pass instead
+        timer.wrap(ops, "_cplx_lrt_dx", lambda g2r, *a, **k: "cgemm_NT_fused_dx" if g2r.dtype == torch.bfloat16 else None)
+        timer.wrap(ops, "prep_kl", lambda *a, **k: "prep_kl" if a[4] else None)
+        timer.wrap(ops, "reparam_fwd", lambda *a, **k: "reparam_fwd")
+        timer.wrap(ops, "reparam_bwd", lambda *a, **k: "reparam_bwd")
 
     torch.manual_seed(0)                       # identical init on every rank (then broadcast)
     layer = rel.CplxLinearVD(IN_F, OUT_F).to(dev)
@@ -714,11 +803,12 @@ def main():
         kl = sum(rel.penalties(layer, reduction="sum"))
         gy_r, gy_i = y.real.detach() * 2, y.imag.detach() * 2      # d(sum |y|^2)/dy
         torch.autograd.backward((y.real, y.imag, kl), (gy_r, gy_i, klw))
-        return kl
+        return kl, y.real.detach(), y.imag.detach()          # (the output planes: for --dump-outputs)
 
-    def exchange(kl):
+    def exchange(out):
+        kl, y_r, y_i = out
         model.sync_gradients()
-        return dp.all_reduce_scalar_mean(kl) if grouped else kl
+        return (dp.all_reduce_scalar_mean(kl) if grouped else kl), y_r, y_i
 
     def step():
         return exchange(compute())
@@ -768,12 +858,12 @@ def main():
     ctypes.CDLL(None).fflush(None)             # (the banner sits in the C library's stdout buffer)
     os.dup2(saved_stdout, 1)
     os.close(saved_stdout)
-    timer.enabled = graphed is None
+    timer.enabled = args.full and graphed is None
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        kl = graphed.replay() if graphed is not None else step()
+        out = graphed.replay() if graphed is not None else step()
         marks[i + 1].record()
     torch.cuda.synchronize()
     if grouped:
@@ -781,7 +871,13 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     timer.enabled = False
-    if graphed is not None:
+    kl = out[0]
+    if args.dump_outputs and rank == 0:
+        named = {"y_real": out[1], "y_imag": out[2], "x_grad_real": x.real.grad, "x_grad_imag": x.imag.grad}
+        named.update(("grad_" + n.replace(".", "_"), p.grad) for n, p in layer.named_parameters())
+        named["kl"] = kl
+        dump_outputs(args.dump_outputs, named)
+    if args.full and graphed is not None:
         timer.enabled = True       # the same launches, eager, HIP events around each: ten steps
         for _ in range(10):
             step()
@@ -795,27 +891,8 @@ def main():
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         value = world * B * args.steps / elapsed
-        launches, launch_frac = gemm_launch_table({k: timer.mean_ms(k) for k in timer.spans}, B, IN_F, OUT_F)
-        cg = [v for k, v in launches.items() if k.startswith("cgemm")]
-        gemm_ms = sum(cg) / len(cg) if cg else None
-        traffic, traffic_per = gemm_traffic() if B == BATCH else (None, None)
-        real_flops = 2.0 * B * IN_F * OUT_F
-        flops = 8.0 * B * IN_F * OUT_F          # algorithmic flop of ONE 4M complex GEMM launch
-        achieved = flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms else None
-        nw = IN_F * OUT_F
-        # the step's three HBM kernels: the calls the step made, re-issued ten times in a graph of their own (see replay_ms)
-        def replayed(key):
-            if grouped:                     # N > 1: other ranks are past this point; nothing extra beside their teardown
-                return timer.mean_ms(key)
-            try:
-                return timer.replay_ms(key)
-            except Exception as e:  # pragma: no cover - an auxiliary number must not take the line down
-                sys.stderr.write(f"bench.py: replay of {key} failed ({type(e).__name__}: {str(e)[:160]}); event spans instead\n")
-                return timer.mean_ms(key)
-        pk, rp_f, rp_b = (replayed(k) for k in ("prep_kl", "reparam_fwd", "reparam_bwd"))
         in_order = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
         per = sorted(in_order)
-        nout = B * OUT_F
         line = {
             "metric": "Cplx-samples/sec fwd+bwd (CplxLinear-4096 + VD)",
             "value": round(value, 1), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
@@ -830,30 +907,11 @@ def main():
                        "kl_weight": KLW, "noise": "in-kernel Philox4x32-7", "launch": mode,
                        "warmup_detail": (f"{max(args.warmup, 3)} eager steps (capture prerequisites) + {max(args.warmup, 1)} untimed replays"
                                          if graphed is not None else f"{args.warmup} untimed eager steps")},
-            "roofline": {"bound": "mfma", "kernel": "gemm_bf16_w4_kernel<CPLX> (4M complex GEMM, one wave per SIMD: fwd NN, dgrad NT + fused LRT term, wgrad TT + fused KL accumulate = 3 launches/step)",
-                         "achieved": round(achieved, 1) if achieved else None, "peak": BF16_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(achieved / BF16_PEAK_TFLOPS, 4) if achieved else None,
-                         "traffic": traffic, "traffic_per_launch": traffic_per, "flop_per_launch": flops,
-                         "avg_launch_ms": round(gemm_ms, 4) if gemm_ms else None,
-                         # every GEMM launch of the step: forward NN, input gradient NT (with the LRT term 2 x ga fused into
-                         # its epilogue: counted with the GEMM's 8 B I O flop only), weight gradient TT; complex (8 B I O
-                         # flop) and the real variance GEMMs (2 B I O flop)
-                         "launch_ms": launches, "launch_frac": launch_frac,
-                         # the headline is a graph replay, inside which HIP events cannot be recorded
-                         "launch_ms_source": ("ten eager steps right after the timed region (same process, same kernels)"
-                                              if graphed is not None else "the timed steps"),
-                         "traffic_source": "profiles/ PMC file of these kernels and shapes (bench.py: gemm_traffic), not this run"},
-            "hbm_kernels_GBps": {
-                # in-step: operand prep + KL sum + KL gradients in one pass (12 B read, 6 + 12 B written)
-                "prep_kl_fused(30B/elt)": round(30 * nw / (pk * 1e-3) / 1e9, 1) if pk else None,
-                "reparam_fwd(10B/out bf16, s2 bf16)": round(10 * nout / (rp_f * 1e-3) / 1e9, 1) if rp_f else None,
-                "reparam_bwd(8B/out bf16, s2 bf16)": round(8 * nout / (rp_b * 1e-3) / 1e9, 1) if rp_b else None,
-                "in_step_source": ("HIP events around the Python calls of ten eager steps (spans include allocation and launch gaps)"
-                                   if grouped else "the step's own calls, ten per hipGraph replay (bench.py: KernelTimer.replay_ms)"),
-                "peak": HBM_PEAK_GBS},
-            "kl": round(float(kl.detach()), 3),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line.update(full_headline_figures(timer, graphed is not None, grouped, B))
+        line["kl"] = round(float(kl.detach()), 3)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["hbm_kernels_GBps"].update(hbm_points(dev))
             line["cfg2_linear"] = cfg2_point(dev)
             line["conv_cfg3"] = conv_point(dev)

@@ -50,11 +50,29 @@ def leaf(*shape, dtype, scale=1.0):
     return (torch.randn(*shape, dtype=dtype) * scale).requires_grad_(True)
 
 
+PART_BYTES = 900 * 1024      # a fixture above this many raw bytes is stored as <name>.part<k>.npz (tests/conftest.py)
+
+
 def save(name, d):
+    """<name>.npz, or -- so that no stored file exceeds 1 MiB -- consecutive runs of its arrays (in order, each run at
+    most PART_BYTES uncompressed) as <name>.part0.npz, <name>.part1.npz, ..."""
     os.makedirs(OUT, exist_ok=True)
-    path = os.path.join(OUT, name + ".npz")
-    np.savez_compressed(path, **d)
-    print(f"{name}: {len(d)} arrays, {os.path.getsize(path) / 1024:.1f} KiB")
+    for old in [name + ".npz"] + [f for f in os.listdir(OUT) if f.startswith(name + ".part")]:
+        if os.path.exists(os.path.join(OUT, old)):
+            os.remove(os.path.join(OUT, old))
+    parts, size = [{}], 0
+    for k, v in d.items():
+        nbytes = np.asarray(v).nbytes
+        if parts[-1] and size + nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += nbytes
+    paths = [os.path.join(OUT, name + ".npz")] if len(parts) == 1 else \
+        [os.path.join(OUT, f"{name}.part{i}.npz") for i in range(len(parts))]
+    for path, part in zip(paths, parts):
+        np.savez_compressed(path, **part)
+    print(f"{name}: {len(d)} arrays, {sum(os.path.getsize(p) for p in paths) / 1024:.1f} KiB in {len(paths)} file(s)")
 
 
 # --------------------------------------------------------------------------- #
@@ -1118,10 +1136,29 @@ def gen_x3():
     save("x3", d)
 
 
+def gen_state_dict():
+    """The reference's own state_dict (keys in order, shapes, dtypes, values) of the model that
+    tests/test_host_api.py::test_state_dicts_travel_between_this_package_and_the_reference builds with this package,
+    and (keys __y_real / __y_imag) the reference's eval-mode output of its vd(lin(x)) part for x = 1 + 0i."""
+    torch.manual_seed(0)
+    net = torch.nn.Sequential()
+    net.add_module("lin", CplxLinear(6, 5))
+    net.add_module("vd", rel.CplxLinearVD(5, 4))
+    net.add_module("conv", CplxConv2d(3, 2, 3))
+    net.add_module("bn", CplxBatchNorm2d(2))
+    net.add_module("ard", rel.LinearARD(4, 3))
+    d = {k: npy(v) for k, v in net.state_dict().items()}
+    net.eval()
+    y = net.vd(net.lin(C(torch.ones(2, 6), torch.zeros(2, 6))))      # what the reference evaluates on these parameters
+    d["__y_real"], d["__y_imag"] = npy(y.real), npy(y.imag)
+    save("state_dict", d)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(1)  # reproducible summation order
     gens = dict(linear=gen_linear, lrt_linear=gen_lrt_linear, penalty=gen_penalty, conv=gen_conv,
                 batchnorm=gen_batchnorm, api=gen_api, extras=gen_extras, bilinear=gen_bilinear, conv3d=gen_conv3d, conv_transpose=gen_conv_transpose,
-                r02=gen_r02, trajectory=gen_trajectory, trajectory_conv=gen_trajectory_conv, x3=gen_x3)
+                r02=gen_r02, trajectory=gen_trajectory, trajectory_conv=gen_trajectory_conv, x3=gen_x3,
+                state_dict=gen_state_dict)
     for name in (sys.argv[1:] or list(gens)):
         gens[name]()

@@ -1,21 +1,21 @@
 #!/bin/bash
 # Round-4 evidence for bench.py (run on the GPU box, outputs under gpurun_out/r04p/ -> copied to profiles/):
-#  1. rocprofv3 --kernel-trace --stats of the DEFAULT bench command           -> bench_n1_kernel_stats.txt (+ the bench line)
+#  1. rocprofv3 --kernel-trace --stats of `bench.py --full`                     -> bench_n1_kernel_stats.txt (+ the bench line)
 #  2. separate --pmc passes (kernel-trace only) of the eager bench step: FETCH_SIZE / WRITE_SIZE per GEMM launch kind
 #     (FETCH_SIZE doubled per the gfx950 note) and MFMA-pipe busy (SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs / per-XCD cycles)
 cd /tmp && export TMPDIR=/tmp
 R="${GRAFT_REPO_ROOT:-/root/repo}"; O=$R/gpurun_out/r04p; mkdir -p $O
-rocprofv3 --kernel-trace --stats -d $O/prof_bench -- python $R/bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+rocprofv3 --kernel-trace --stats -d $O/prof_bench -- python $R/bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 python $R/scripts/rocprof_summary.py $O/prof_bench/*/*_results.db > $O/bench_n1_kernel_stats.txt
 rm -rf $O/prof_bench
 # the same command without the extra points of the line (cfg2 / cfg3 / cfg4 / HBM sizes / CPU leg share kernel names with the
 # headline step and would blur its per-kernel averages): the headline step's kernels only
-rocprofv3 --kernel-trace --stats -d $O/prof_head -- python $R/bench.py --no-cpu-baseline > $O/bench_n1_headline.json 2> $O/bench_n1_headline.err
+rocprofv3 --kernel-trace --stats -d $O/prof_head -- python $R/bench.py --full --no-cpu-baseline > $O/bench_n1_headline.json 2> $O/bench_n1_headline.err
 python $R/scripts/rocprof_summary.py $O/prof_head/*/*_results.db > $O/bench_n1_headline_kernel_stats.txt
 rm -rf $O/prof_head
 for c in FETCH_SIZE WRITE_SIZE "GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES"; do
   n=$(echo $c | tr ' ' '_')
-  timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$n -- python $R/bench.py --steps 6 --warmup 3 --no-cpu-baseline --graph off > $O/pmc_$n.log 2>&1
+  timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$n -- python $R/bench.py --steps 6 --warmup 3 --full --no-cpu-baseline --graph off > $O/pmc_$n.log 2>&1
 done
 cd $R
 python - <<'PY'
@@ -37,7 +37,7 @@ med = lambda k, c: statistics.median(val[(k, c)][2:]) if (k, c) in val else None
 B, I, Oo = 8192, 4096, 4096
 alg_c = {"cgemm_NN": 2 * (B * I + Oo * I) * 2 + 2 * B * Oo * 2, "cgemm_NT": 2 * (B * Oo + Oo * I) * 2 + 2 * B * I * 2,
          "cgemm_TT": 2 * (B * Oo + B * I) * 2 + 2 * Oo * I * 4 * 2}      # TT: fp32 out + the accumulate operand it reads
-out = {"command": "bench.py --steps 6 --warmup 3 --no-cpu-baseline --graph off (eager), rocprofv3 --pmc <counter> --kernel-trace, one pass per counter set; median over the launches after the first two",
+out = {"command": "bench.py --steps 6 --warmup 3 --full --no-cpu-baseline --graph off (eager), rocprofv3 --pmc <counter> --kernel-trace, one pass per counter set; median over the launches after the first two",
        "note": "FETCH_SIZE in KiB, doubled (gfx950: 64 B tallied per 128-B request, MI355X_MICROARCH.md); WRITE_SIZE in KiB; Infinity-Cache hits are not excluded",
        "per_launch": {}, "detail": {}}
 for k in ("cgemm_NN", "cgemm_NT", "cgemm_TT", "rgemm_NN", "rgemm_NT", "rgemm_TT"):

@@ -16,7 +16,18 @@ def pytest_configure(config):
 
 
 def load_golden(name):
-    return dict(np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False))
+    """tests/golden/<name>.npz, or the union of <name>.part0.npz, <name>.part1.npz, ... (a large fixture is stored in
+    parts of at most 1 MiB: oracle/gen_golden.py:save)."""
+    path = os.path.join(GOLDEN, name + ".npz")
+    if os.path.exists(path):
+        return dict(np.load(path, allow_pickle=False))
+    d, k = {}, 0
+    while os.path.exists(os.path.join(GOLDEN, f"{name}.part{k}.npz")):
+        d.update(np.load(os.path.join(GOLDEN, f"{name}.part{k}.npz"), allow_pickle=False))
+        k += 1
+    if not d:
+        raise FileNotFoundError(path)
+    return d
 
 
 @pytest.fixture(scope="session")

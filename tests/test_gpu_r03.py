@@ -173,7 +173,7 @@ def test_bench_py_runs_with_two_ranks_and_with_rccl():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    common = ["--steps", "2", "--warmup", "1", "--batch", "512", "--no-cpu-baseline"]
+    common = ["--steps", "2", "--warmup", "1", "--batch", "512", "--full", "--no-cpu-baseline"]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29547", os.path.join(root, "bench.py"),
                         "--gpus", "2", "--backend", "gloo", "--share-device"] + common,
