@@ -12,11 +12,11 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CPLXAMD_LIB") or os.path.join(_HERE, "libcplxamd.so")   # env: A/B builds
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 F32, BF16, F16 = 0, 1, 2
 KL_KINDS = {"real_vd": 0, "real_ard": 1, "cplx_vd": 2, "cplx_ard": 3, "cplx_vd_approx": 4,
-            "cplx_vd_scalefree": 5, "cplx_vd_bogus": 6}
+            "cplx_vd_scalefree": 5, "cplx_vd_bogus": 6, "real_l0": 7, "real_l1": 8}
 
 _P, _I, _L, _U, _F, _D = c_void_p, c_int, c_int64, c_uint64, c_float, c_double
 
@@ -43,6 +43,11 @@ SIGNATURES = {
     "cplxamd_lrt_reparam_bwd_cols": [_P, _P, _P, _P, _P, _U, _U, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     "cplxamd_philox_advance": [_P, _P, _P],
     "cplxamd_philox_normal": [_P, _P, _U, _U, _L, _P],
+    "cplxamd_philox_uniform": [_P, _U, _U, _L, _P],
+    "cplxamd_l0_gate_fwd": [_P, _P, _P, _U, _U, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P],
+    "cplxamd_l0_gate_bwd_ws_bytes": [_L, _I],
+    "cplxamd_l0_gate_bwd": [_P, _P, _P, _P, _U, _U, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _L, _P],
+    "cplxamd_l1_mask": [_P, _F, _P, _P, _P, _L, _P],
     "cplxamd_cgemm": [_P, _P, _L, _L, _P, _P, _L, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I,
                       _I, _I, _I, _P, _L, _P],
     "cplxamd_cgemm_ex": [_P, _P, _L, _L, _P, _P, _L, _L, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I,
@@ -168,7 +173,7 @@ SIGNATURES = {
     "cplxamd_bn_fwd_partials": [_P, _P, _P, _P, _L, _I, _L, _P, _P, _P, _P, _P, _I, _F, _F, _P, _P, _I, _P, _L, _P],
     "cplxamd_bn_bwd_sync": [_P, _P, _P, _P, _P, _P, _L, _I, _L, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _P],
 }
-_RESTYPES = {"cplxamd_absmax_ws_bytes": c_int64, "cplxamd_conv2d_cl2_mom_chunks": c_int64, "cplxamd_conv2d_cl2_mom_chunks_fl": c_int64, "cplxamd_vd_kl_ws_bytes": c_int64, "cplxamd_lrt_reparam_bwd_cols_ws_bytes": c_int64, "cplxamd_bn_ws_bytes": c_int64,
+_RESTYPES = {"cplxamd_absmax_ws_bytes": c_int64, "cplxamd_conv2d_cl2_mom_chunks": c_int64, "cplxamd_conv2d_cl2_mom_chunks_fl": c_int64, "cplxamd_vd_kl_ws_bytes": c_int64, "cplxamd_lrt_reparam_bwd_cols_ws_bytes": c_int64, "cplxamd_l0_gate_bwd_ws_bytes": c_int64, "cplxamd_bn_ws_bytes": c_int64,
              "cplxamd_conv2d_wgrad_ws_bytes": c_int64, "cplxamd_conv2d_bf16_wgrad_ws_bytes": c_int64, "cplxamd_colsum_ws_bytes": c_int64, "cplxamd_gemm_ws_bytes": c_int64,
              "cplxamd_cgemm3m_ws_bytes": c_int64,
              "cplxamd_conv2d_nhwc_wgrad_ws_bytes": c_int64,

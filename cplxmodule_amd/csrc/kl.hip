@@ -152,6 +152,24 @@ __device__ __forceinline__ float kl_slope(float t) {
   return softplus_grad_f(t);
 }
 
+// ABI 25: the penalties of ONE parameter p (no log_alpha of a weight involved), value and d/dp
+//   L0  extensions/real/ell_zero.py:73-88  sigmoid(shift - log_alpha), shift = -beta log(-gamma / zeta) = 0.66 log 11
+//   L1  extensions/real/lasso.py:7-9       |w|, torch.abs's gradient sign(w) (0 at 0)
+constexpr float kL0Shift = 1.5826108800469247f;
+template <int KIND> __device__ __forceinline__ constexpr bool kl_one_param() {
+  return KIND == CPLXAMD_KL_REAL_L0 || KIND == CPLXAMD_KL_REAL_L1;
+}
+template <int KIND>
+__device__ __forceinline__ float one_param_value(float p, float& slope) {
+  if (KIND == CPLXAMD_KL_REAL_L0) {
+    const float s = sigmoid_f(kL0Shift - p);
+    slope = -(s * (1.0f - s));
+    return s;
+  }
+  slope = p > 0.0f ? 1.0f : (p < 0.0f ? -1.0f : 0.0f);
+  return fabsf(p);
+}
+
 template <bool CPLX>
 __device__ __forceinline__ void weight_grad(float fp, float wr, float wi, float theta,
                                             float& gwr, float& gwi) {
@@ -265,7 +283,7 @@ __device__ __forceinline__ f4 ld4g(const float* p) {
 
 template <int KIND, bool VALUE, bool GRAD>
 __global__ __launch_bounds__(kKlThreads) void kl_kernel(KlArgs a) {
-  constexpr bool CPLX = KIND >= CPLXAMD_KL_CPLX_VD;
+  constexpr bool CPLX = KIND >= CPLXAMD_KL_CPLX_VD && KIND <= CPLXAMD_KL_CPLX_VD_BOGUS;
   constexpr float kLs = kl_ls2_term<KIND>();
   __shared__ double red[kKlThreads / 64];
   const int64_t n4 = a.n >> 2;
@@ -305,6 +323,21 @@ __global__ __launch_bounds__(kKlThreads) void kl_kernel(KlArgs a) {
       }
       done = !tiny;
       if (VALUE && done) part = (val.v[0] + val.v[1]) + (val.v[2] + val.v[3]);
+    }
+    if constexpr (kl_one_param<KIND>()) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float sl;
+        const float v = one_param_value<KIND>(KIND == CPLXAMD_KL_REAL_L0 ? ls.v[j] : wr.v[j], sl);
+        if (VALUE) { val.v[j] = v; part += v; }
+        if (GRAD) {
+          const float g = sl * ge.v[j] * gs;
+          d_ls.v[j] = KIND == CPLXAMD_KL_REAL_L0 ? g : 0.0f;
+          d_wr.v[j] = KIND == CPLXAMD_KL_REAL_L1 ? g : 0.0f;
+          d_wi.v[j] = 0.0f;
+        }
+      }
+      done = true;
     }
     if (!done) {
       part = 0.0f;
@@ -369,6 +402,19 @@ __global__ __launch_bounds__(kKlThreads) void kl_kernel(KlArgs a) {
     if (i < a.n) {
       const float wr = a.wr[i], ls = a.ls2[i];
       const float wi = CPLX ? a.wi[i] : 0.0f;
+      if constexpr (kl_one_param<KIND>()) {
+        float sl;
+        const float v = one_param_value<KIND>(KIND == CPLXAMD_KL_REAL_L0 ? ls : wr, sl);
+        if (VALUE) {
+          acc += (double)v;
+          if (a.out_elem) a.out_elem[i] = v;
+        }
+        if (GRAD) {
+          const float g = sl * (a.g_elem ? a.g_elem[i] : 1.0f) * gs;
+          if (a.g_ls2) a.g_ls2[i] = KIND == CPLXAMD_KL_REAL_L0 ? g : 0.0f;
+          if (a.g_wr) a.g_wr[i] = KIND == CPLXAMD_KL_REAL_L1 ? g : 0.0f;
+        }
+      } else {
       float theta;
       const float t = -log_alpha_of<CPLX, false>(ls, wr, wi, theta);
       if (VALUE) {
@@ -384,6 +430,7 @@ __global__ __launch_bounds__(kKlThreads) void kl_kernel(KlArgs a) {
         if (a.g_ls2) a.g_ls2[i] = kLs * ge * gs - fp;
         if (a.g_wr) a.g_wr[i] = gwr;
         if (CPLX && a.g_wi) a.g_wi[i] = gwi;
+      }
       }
     }
   }
@@ -427,6 +474,12 @@ static int launch_kl(int kind, const KlArgs& a, int grid, hipStream_t st) {
     case CPLXAMD_KL_CPLX_VD_BOGUS:
       kl_kernel<CPLXAMD_KL_CPLX_VD_BOGUS, VALUE, GRAD><<<grid, kKlThreads, 0, st>>>(a);
       break;
+    case CPLXAMD_KL_REAL_L0:
+      kl_kernel<CPLXAMD_KL_REAL_L0, VALUE, GRAD><<<grid, kKlThreads, 0, st>>>(a);
+      break;
+    case CPLXAMD_KL_REAL_L1:
+      kl_kernel<CPLXAMD_KL_REAL_L1, VALUE, GRAD><<<grid, kKlThreads, 0, st>>>(a);
+      break;
     default:
       return CPLXAMD_EINVAL;
   }
@@ -451,8 +504,8 @@ __global__ __launch_bounds__(kKlThreads) void prep_kernel(const float* wr, const
 }
 
 static bool kl_args_ok(const float* wr, const float* wi, const float* ls2, int kind, int64_t n) {
-  if (!wr || !ls2 || n < 0 || kind < 0 || kind > CPLXAMD_KL_CPLX_VD_BOGUS) return false;
-  const bool cplx = kind >= CPLXAMD_KL_CPLX_VD;
+  if (!wr || !ls2 || n < 0 || kind < 0 || kind > CPLXAMD_KL_REAL_L1) return false;
+  const bool cplx = kind >= CPLXAMD_KL_CPLX_VD && kind <= CPLXAMD_KL_CPLX_VD_BOGUS;
   return cplx ? wi != nullptr : true;
 }
 

@@ -26,44 +26,6 @@ namespace cplxamd {
 
 constexpr int kRpThreads = 256;
 
-// A value every lane read from the same address, pinned to scalar registers: the compiler cannot prove that a loaded
-// stream position is wave-uniform and would otherwise run Philox's key schedule (2 adds per round) on the vector ALU --
-// 14 of ~70 instructions per call in kernels that PMC shows 93 % VALU-busy (profiles/r03_reparam_pmc.txt).
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-  return ((uint64_t)hi << 32) | lo;
-}
-
-struct u32x4 { uint32_t v[4]; };
-
-__device__ __forceinline__ u32x4 philox4x32(uint64_t ctr_lo, uint64_t ctr_hi, uint64_t key) {
-  uint32_t c0 = (uint32_t)ctr_lo, c1 = (uint32_t)(ctr_lo >> 32);
-  uint32_t c2 = (uint32_t)ctr_hi, c3 = (uint32_t)(ctr_hi >> 32);
-  uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < kPhiloxRounds; ++r) {
-    // one 32x32->64 product each (v_mad_u64_u32) instead of a mul_lo + mul_hi pair
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t lo0 = (uint32_t)p0, hi0 = (uint32_t)(p0 >> 32);
-    const uint32_t lo1 = (uint32_t)p1, hi1 = (uint32_t)(p1 >> 32);
-    // three-input XOR in one instruction (v_bitop3_b32, truth table 0x96)
-    c0 = __builtin_amdgcn_bitop3_b32(hi1, c1, k0, 0x96);
-    c1 = lo1;
-    c2 = __builtin_amdgcn_bitop3_b32(hi0, c3, k1, 0x96);
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return u32x4{{c0, c1, c2, c3}};
-}
-
-__device__ __forceinline__ float u01(uint32_t x) {
-  // ((x >> 8) + 0.5) * 2^-24 as ONE fused multiply-add: bit-identical to the add-then-multiply of the stream definition
-  // (below 2^23 both are exact; from 2^23 on the sum is a tie that either form rounds to the same even neighbour)
-  return fmaf((float)(x >> 8), 5.9604644775390625e-08f, 2.98023223876953125e-08f);
-}
-
 // scale = 1 for real noise, 1/sqrt(2) for complex
 __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float scale, float& z0,
                                            float& z1) {

@@ -7,3 +7,4 @@ from .complex import CplxConv1dVD, CplxConv1dARD  # noqa: F401
 from .complex import CplxBilinearVD, CplxBilinearARD, CplxConv3dVD, CplxConv3dARD  # noqa: F401
 from .complex import torch_expi  # noqa: F401
 from . import extensions  # noqa: F401
+from .extensions import LinearL0, LinearLASSO  # noqa: F401

@@ -1,4 +1,5 @@
-"""Alternative complex variational-dropout penalties (reference:
+"""LinearL0 and LinearLASSO (extensions/real.py; reference: cplxmodule/nn/relevance/extensions/real/), and the
+alternative complex variational-dropout penalties (reference:
 cplxmodule/nn/relevance/extensions/complex.py:18-206).  Same layers and forward pass as the
 Cplx*VD layers; only the KL kind evaluated by csrc/kl.hip differs:
   *VDApprox     softplus(-la) + 0.57810 sigmoid(1.36526 (-la) - 1.45926)              (:113-117)
@@ -7,9 +8,10 @@ Cplx*VD layers; only the KL kind evaluated by csrc/kl.hip differs:
                 (the reference's way around its host-side Ei; here the exact penalty costs the same)
 """
 from .. import complex as _base
+from .real import LinearL0, LinearLASSO
 
 _KINDS = {"Approx": "cplx_vd_approx", "ScaleFree": "cplx_vd_scalefree", "Bogus": "cplx_vd_bogus"}
-__all__ = []
+__all__ = ["LinearL0", "LinearLASSO"]
 
 for _layer in ("Linear", "Bilinear", "Conv1d", "Conv2d", "Conv3d"):
     _parent = getattr(_base, f"Cplx{_layer}VD")

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define CPLXAMD_ABI_VERSION 24
+#define CPLXAMD_ABI_VERSION 25
 
 /* element types of activations / outputs */
 enum { CPLXAMD_F32 = 0, CPLXAMD_BF16 = 1,
@@ -44,7 +44,12 @@ enum {
   /* SURVEY 8(f) row 4, cplxmodule/nn/relevance/extensions/complex.py: */
   CPLXAMD_KL_CPLX_VD_APPROX = 4,    /* :113-117 softplus-sigmoid approximation          */
   CPLXAMD_KL_CPLX_VD_SCALEFREE = 5, /* :43-46   log|w| - log_sigma2 - Ei(-1/alpha) / 2  */
-  CPLXAMD_KL_CPLX_VD_BOGUS = 6      /* :142-160 value -log_alpha (Ei dropped), exact slope  */
+  CPLXAMD_KL_CPLX_VD_BOGUS = 6,     /* :142-160 value -log_alpha (Ei dropped), exact slope  */
+  /* ABI 25, cplxmodule/nn/relevance/extensions/real/: penalties of ONE parameter p, passed as both wr and log_sigma2;
+   * only the gradient pointer named here is written (pass NULL for the other) */
+  CPLXAMD_KL_REAL_L0 = 7,   /* ell_zero.py:73-88  sigmoid(beta log(zeta / -gamma) - log_alpha), p = log_alpha,
+                                                   gradient -> g_log_sigma2                                  */
+  CPLXAMD_KL_REAL_L1 = 8    /* lasso.py:7-9       |w| (torch.abs's gradient sign(w), 0 at 0), p = w, -> g_wr  */
 };
 
 /* error codes (negative; positive values are hipError_t) */
@@ -200,6 +205,47 @@ int cplxamd_philox_advance(uint64_t* state, uint64_t* used, void* stream);
 /* Writes the Philox noise itself (float32), for tests: real (eps_i NULL) or complex. */
 int cplxamd_philox_normal(float* eps_r, float* eps_i, uint64_t seed, uint64_t offset,
                           int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * L0 hard-concrete gate (ABI 25; csrc/l0.hip).
+ * Replaces: LinearL0.forward / gate / relevance / sparsity   nn/relevance/extensions/real/ell_zero.py:90-170
+ *           LinearLASSO.relevance / sparsity                  nn/relevance/extensions/real/lasso.py:11-19
+ *   train  z = clamp(1.2 sigmoid((log u - log(1 - u) - log_alpha) / 0.66) - 0.1, 0, 1)
+ *   eval   z = clamp(1.2 sigmoid(-log_alpha) - 0.1, 0, 1)
+ * Uniform stream (DESIGN.md "uniform stream"): element e (flat index of the [rows][cols] operand, = the flat index of
+ * the reference's `u`) takes u01(Philox4x32-7(counter (e >> 2, offset), key seed)[e & 3]), u01(x) = ((x >> 8) + 0.5)
+ * 2^-24.  `state` (nullable) is a device uint64[2] {seed, offset} read instead of the two arguments (graph capture),
+ * as in cplxamd_lrt_reparam_fwd.  `u` (nullable, float32 [rows][cols]) supplies the uniforms instead (parity mode).
+ * mode: CPLXAMD_L0_COLS -- log_alpha is [cols], one gate parameter per column (the input / output groups), else
+ * [rows][cols] (group None); CPLXAMD_L0_TRAIN -- the stochastic gate, else the eval gate (u, seed, offset, state
+ * ignored); CPLXAMD_L0_HARD (forward only) -- z > 0 ? 1 : 0.
+ *   cplxamd_l0_gate_fwd   out = A (.) z (+ bias[c], COLS only), float32 arithmetic; a NULL: out = z (the relevance
+ *                         mask).  a_dtype / out_dtype: CPLXAMD_F32 or CPLXAMD_BF16.  total (nullable, float64) = sum of
+ *                         out, in a fixed order; ws: cplxamd_vd_kl_ws_bytes() bytes when total is given.
+ *   cplxamd_l0_gate_bwd   the gate regenerated from the same (u | seed, offset, state): da = D (.) z and az = A (.) z
+ *                         (both nullable), d_log_alpha = D (.) A (.) dz/dlog_alpha elementwise, or with COLS its sum
+ *                         over the rows per column -- per-workgroup partials in ws (cplxamd_l0_gate_bwd_ws_bytes(rows,
+ *                         cols) bytes) summed in a fixed order, no atomics: repeated calls give the same bits.  The
+ *                         clamp passes the gradient where 0 <= pre-clamp value <= 1 (torch.clamp).  Pointers 16-byte
+ *                         aligned.  Dtype combinations (d, a, da, az; an output passed as NULL takes the dtype of
+ *                         its sibling, else of a): all float32; float32 d with bf16 a, da, az; bf16 d, da, az with
+ *                         float32 a; all bf16.
+ *   cplxamd_l1_mask       mask[n] (bool bytes, nullable) = log(|w| + 1e-20) >= threshold, correctly rounded log;
+ *                         count (nullable, float64) = #ones; ws: cplxamd_vd_kl_ws_bytes() bytes when count is given.
+ *   cplxamd_philox_uniform  u[n] = the uniform stream itself (tests).
+ * HBM (group None, float32 W, bf16 operand): forward 10 B per weight, backward 20 B per weight.
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_L0_COLS = 1, CPLXAMD_L0_TRAIN = 2, CPLXAMD_L0_HARD = 4 };
+int cplxamd_l0_gate_fwd(const void* a, const float* log_alpha, const float* u, uint64_t seed, uint64_t offset,
+                        const uint64_t* state, const float* bias, void* out, int64_t rows, int cols, int mode,
+                        int a_dtype, int out_dtype, double* total, void* ws, void* stream);
+int64_t cplxamd_l0_gate_bwd_ws_bytes(int64_t rows, int cols);
+int cplxamd_l0_gate_bwd(const void* d, const void* a, const float* log_alpha, const float* u, uint64_t seed,
+                        uint64_t offset, const uint64_t* state, void* da, void* az, float* d_log_alpha, int64_t rows,
+                        int cols, int mode, int d_dtype, int a_dtype, int da_dtype, int az_dtype, void* ws,
+                        int64_t ws_bytes, void* stream);
+int cplxamd_l1_mask(const float* w, float threshold, uint8_t* mask, double* count, void* ws, int64_t n, void* stream);
+int cplxamd_philox_uniform(float* u, uint64_t seed, uint64_t offset, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * K1/K4  complex and real GEMM,  C[m,n] = sum_k A[m,k] * op(B[n,k]) (+ bias[n]).
