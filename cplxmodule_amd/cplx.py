@@ -533,6 +533,100 @@ def to_concatenated_real(input, flatten=None, dim=-1):
     return torch.cat([input.real, input.imag], dim=dim)
 
 
+# ---- joining / splitting (cplxmodule/cplx.py:379-448): plane-wise torch plumbing, any device --------------------------
+def cat(tensors, dim):
+    tensors = [*map(Cplx, tensors)]
+    return Cplx(torch.cat([z.real for z in tensors], dim=dim), torch.cat([z.imag for z in tensors], dim=dim))
+
+
+def split(input, split_size_or_sections, dim=0):
+    """see documentation for `torch.split`"""
+    return tuple(Cplx(re, im) for re, im in zip(torch.split(input.real, split_size_or_sections, dim),
+                                                torch.split(input.imag, split_size_or_sections, dim)))
+
+
+def chunk(input, chunks, dim=0):
+    """see documentation for `torch.chunk`"""
+    return tuple(Cplx(re, im) for re, im in zip(torch.chunk(input.real, chunks, dim), torch.chunk(input.imag, chunks, dim)))
+
+
+def stack(tensors, dim):
+    tensors = [*map(Cplx, tensors)]
+    return Cplx(torch.stack([z.real for z in tensors], dim=dim), torch.stack([z.imag for z in tensors], dim=dim))
+
+
+def unbind(input, dim=0):
+    """see documentation for `torch.unbind`"""
+    return tuple(Cplx(re, im) for re, im in zip(torch.unbind(input.real, dim), torch.unbind(input.imag, dim)))
+
+
+def take(input, index):
+    """see documentation for `torch.take`"""
+    return Cplx(torch.take(input.real, index), torch.take(input.imag, index))
+
+
+def narrow(input, dim, start, length):
+    """see documentation for `torch.narrow`"""
+    return Cplx(torch.narrow(input.real, dim, start, length), torch.narrow(input.imag, dim, start, length))
+
+
+def squeeze(input, dim=None):
+    """see documentation for `torch.squeeze`"""
+    return input.squeeze(dim)
+
+
+def unsqueeze(input, dim):
+    """see documentation for `torch.unsqueeze`"""
+    return Cplx(torch.unsqueeze(input.real, dim), torch.unsqueeze(input.imag, dim))
+
+
+# ---- elementary functions (cplxmodule/cplx.py:482-541): one fused kernel each way (csrc/cplxfn.hip) ----------------------
+def _elementary(input, fn):
+    return Cplx(*ops.CplxFnFn.apply(input.real, input.imag, fn))
+
+
+def exp(input):
+    r"""e^z = e^x (cos y + i sin y)."""
+    return _elementary(input, "exp")
+
+
+def log(input):
+    r"""Principal logarithm (log|z|, atan2(y, x)); |z| is formed with scaling, so it never overflows or underflows."""
+    return _elementary(input, "log")
+
+
+def sin(input):
+    r"""sin z = sin x cosh y + i cos x sinh y."""
+    return _elementary(input, "sin")
+
+
+def cos(input):
+    r"""cos z = cos x cosh y - i sin x sinh y."""
+    return _elementary(input, "cos")
+
+
+def tan(input):
+    r"""tan z = -i tanh(iz).  Finite wherever the true value is: the reference's sin(z) / cos(z) gives NaN once cosh(y)
+    overflows (tan(x + 100j) there is nan, here ~1j)."""
+    return _elementary(input, "tan")
+
+
+def sinh(input):
+    r"""sinh z = sinh x cos y + i cosh x sin y."""
+    return _elementary(input, "sinh")
+
+
+def cosh(input):
+    r"""cosh z = cosh x cos y + i sinh x sin y."""
+    return _elementary(input, "cosh")
+
+
+def tanh(input):
+    r"""tanh z in Kahan's form, saturated to (sign x, 4 sin y cos y e^{-2|x|}) for |x| > 11.  Finite wherever the true
+    value is: the reference's sinh(z) / cosh(z) gives NaN once cosh(x) overflows (tanh(100 + 1j) there is nan, here ~1)."""
+    return _elementary(input, "tanh")
+
+
 def modrelu(input, threshold=0.5):
     """Soft-threshold of the modulus, phase kept: z * relu(1 - threshold / max(|z|, 1e-5))
     (cplxmodule/cplx.py:565-616; note the reference's flipped sign convention).  `threshold` is a

@@ -163,6 +163,18 @@ def cplx_abs(zr, zi):
     return torch.norm(torch.stack([zr, zi], dim=0), p=2, dim=0)
 
 
+_CPLX_FN = {"exp": torch.exp, "log": torch.log, "sin": torch.sin, "cos": torch.cos, "tan": torch.tan, "sinh": torch.sinh,
+            "cosh": torch.cosh, "tanh": torch.tanh}
+
+
+def cplx_fn(zr, zi, fn):
+    """ops.CplxFnFn for float64 (cplx.py:482-541): torch's complex128 function on torch.complex(zr, zi) under autograd,
+    differentiable to any order; the planes of the result are views of it."""
+    _chk(zr, zi)
+    w = _CPLX_FN[fn](torch.complex(zr, zi))
+    return w.real, w.imag
+
+
 def log_alpha(ls2, wr, wi):
     """complex/base.py:27-31, real/base.py:23-26."""
     theta = torch.abs(wr) if wi is None else cplx_abs(wr, wi)

@@ -1739,6 +1739,58 @@ def cplx_mul(ar, ai, br, bi, div=False):
     return CplxMulFn.apply(ar, ai, br, bi, bool(div))
 
 
+class CplxFnFn(torch.autograd.Function):
+    """cplx.exp / log / sin / cos / tan / sinh / cosh / tanh (cplxmodule/cplx.py:482-541; the reference: 4 to ~10 elementwise
+    torch kernels each way) in one launch forward and one backward (csrc/cplxfn.hip).  `fn` is a key of _lib.CPLX_FN.  The
+    backward recomputes f'(z) from the input, saved AS GIVEN (as CplxMulFn does); under create_graph it is spelled with the
+    public functions and Cplx products on those saved tensors, so it is differentiable to any order and still runs the
+    kernels."""
+
+    @staticmethod
+    def forward(ctx, zr, zi, fn):
+        require_device(zr, zi)
+        if zr.dtype != zi.dtype or zr.shape != zi.shape:
+            raise _lib.CplxAmdError(f"complex planes differ: {zr.dtype} {tuple(zr.shape)} vs {zi.dtype} {tuple(zi.shape)}")
+        code = dtype_code(zr)
+        ctx.fmt = fmt = _layout_of(zr)
+        a, b = _al16(_cf(zr, fmt)), _al16(_cf(zi, fmt))
+        yr, yi = torch.empty_like(a), torch.empty_like(b)
+        call("cplxamd_cplx_fn_fwd", ptr(a), ptr(b), ptr(yr), ptr(yi), a.numel(), _lib.CPLX_FN[fn], code, stream_ptr())
+        ctx.fn = fn
+        ctx.save_for_backward(zr, zi)
+        return yr, yi
+
+    @staticmethod
+    def backward(ctx, gr, gi):
+        zr, zi = ctx.saved_tensors
+        gr = torch.zeros_like(zr) if gr is None else gr
+        gi = torch.zeros_like(zi) if gi is None else gi
+        if torch.is_grad_enabled():
+            from .cplx import Cplx
+            dz = CplxFnFn.deriv(ctx.fn, Cplx(zr, zi)).conj * Cplx(gr, gi)
+            return dz.real, dz.imag, None
+        dense = lambda t: _al16(_cf(t, ctx.fmt))  # noqa: E731
+        a, b, gr, gi = dense(zr), dense(zi), dense(gr.to(zr.dtype)), dense(gi.to(zr.dtype))
+        dzr, dzi = torch.empty_like(a), torch.empty_like(b)
+        call("cplxamd_cplx_fn_bwd", ptr(a), ptr(b), ptr(gr), ptr(gi), ptr(dzr), ptr(dzi), a.numel(), _lib.CPLX_FN[ctx.fn],
+             dtype_code(a), stream_ptr())
+        return dzr, dzi, None
+
+    @staticmethod
+    def deriv(fn, z):
+        """f'(z) from the public functions and Cplx products (differentiable): exp z, 1 / z, cos z, -sin z, 1 / cos(z)^2,
+        cosh z, sinh z, 1 / cosh(z)^2."""
+        from . import cplx
+        if fn in ("tan", "tanh"):
+            c = cplx.cos(z) if fn == "tan" else cplx.cosh(z)
+            return 1 / (c * c)
+        if fn == "log":
+            return 1 / z
+        if fn == "cos":
+            return -cplx.sin(z)
+        return getattr(cplx, {"exp": "exp", "sin": "cos", "sinh": "cosh", "cosh": "sinh"}[fn])(z)
+
+
 class SplitReluFn(torch.autograd.Function):
     """torch.nn.ReLU on both planes (CplxToCplx[torch.nn.ReLU], cplxmodule/nn/modules/base.py:167-199): one launch
     forward, one backward (the mask is read off the saved outputs, as aten's threshold_backward does)."""
@@ -1878,6 +1930,7 @@ PenaltySumFn = Route(PenaltySumFn, "penalty_sum")
 AbsFn = Route(AbsFn, "cplx_abs")
 ExpiFn = Route(ExpiFn, "expi")
 MaskMulFn = Route(MaskMulFn, "mask_mul")
+CplxFnFn = Route(CplxFnFn, "cplx_fn")
 _relevance_mask32 = relevance_mask
 
 

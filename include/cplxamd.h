@@ -872,6 +872,26 @@ int cplxamd_modrelu_bwd(const void* zr, const void* zi, const float* tau, float 
 int cplxamd_cplx_dropout(const void* xr, const void* xi, void* yr, void* yi, double p, uint64_t seed,
                          uint64_t offset, const uint64_t* state, int64_t n, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Complex elementary functions (cplx.exp / log / sin / cos / tan / sinh / cosh / tanh, cplxmodule/cplx.py:482-541; csrc/
+ * cplxfn.hip), one launch each way.  Added after ABI 25 was published: these are new exports only, nothing existing
+ * changes, so the version stays 25 and every consumer of ABI 25 keeps working.
+ *   cplxamd_cplx_fn_fwd  y = f(z)
+ *   cplxamd_cplx_fn_bwd  dz = conj(f'(z)) g   (the gradient of the real pair (re, im), as autograd defines it), f'
+ *                        recomputed from the saved input z
+ * float32 arithmetic for F32 and BF16 (BF16 rounded once on store).  tan and tanh stay finite wherever the true value is
+ * (Kahan's form, saturated past |Re| = 11 for tanh, |Im| = 11 for tan), where the reference's sin / cos and sinh / cosh
+ * quotients give NaN; exp, sin, cos, sinh and cosh may give inf where one of the reference's real factors overflows.
+ * n complex elements in planes sharing one dense layout, 16-byte aligned.  Checked before any launch: a NULL pointer with
+ * n > 0, n < 0, an unknown fn or a dtype other than F32 / BF16 -> CPLXAMD_EINVAL; n == 0 -> 0.
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_FN_EXP = 0, CPLXAMD_FN_LOG, CPLXAMD_FN_SIN, CPLXAMD_FN_COS,
+       CPLXAMD_FN_TAN, CPLXAMD_FN_SINH, CPLXAMD_FN_COSH, CPLXAMD_FN_TANH };
+int cplxamd_cplx_fn_fwd(const void* z_r, const void* z_i, void* y_r, void* y_i,
+                        int64_t n, int fn, int dtype, void* stream);
+int cplxamd_cplx_fn_bwd(const void* z_r, const void* z_i, const void* g_r, const void* g_i,
+                        void* dz_r, void* dz_i, int64_t n, int fn, int dtype, void* stream);
+
 /* Complex abs-max pooling (cplx.max_poolnd, cplx.py:1114-1175): in every window the element of
  * largest modulus keeps both its parts (first maximum in row-major window order, as torch).
  * pool = int[14]: B, C, H, W, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw.  idx: int32 [B, C, Ho, Wo],
