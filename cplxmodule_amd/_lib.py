@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CPLXAMD_LIB") or os.path.join(_HERE, "libcplxamd.so")   # env: A/B builds
 ABI_VERSION = 25
 
-F32, BF16, F16 = 0, 1, 2
+F32, BF16, F16, F64 = 0, 1, 2, 3
 KL_KINDS = {"real_vd": 0, "real_ard": 1, "cplx_vd": 2, "cplx_ard": 3, "cplx_vd_approx": 4,
             "cplx_vd_scalefree": 5, "cplx_vd_bogus": 6, "real_l0": 7, "real_l1": 8}
 
@@ -175,6 +175,10 @@ SIGNATURES = {
     # still ABI 25 (exports added, nothing changed): the complex elementary functions
     "cplxamd_cplx_fn_fwd": [_P, _P, _P, _P, _L, _I, _I, _P],
     "cplxamd_cplx_fn_bwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _P],
+    # still ABI 25: the Welch spectra (F64 = 3 is their dtype code only)
+    "cplxamd_welch_plan": [_L, _L, _L, _I, _P, _P],
+    "cplxamd_welch_fwd": [_P, _P, _L, _L, _L, _L, _P, _L, _L, _I, _D, _P, _P, _L, _I, _P],
+    "cplxamd_welch_bwd": [_P, _P, _L, _L, _L, _L, _P, _L, _L, _I, _D, _P, _P, _P, _L, _L, _P, _L, _I, _P],
 }
 # function codes of cplxamd_cplx_fn_fwd / _bwd (CPLXAMD_FN_*)
 CPLX_FN = {"exp": 0, "log": 1, "sin": 2, "cos": 3, "tan": 4, "sinh": 5, "cosh": 6, "tanh": 7}

@@ -1,1 +1,1 @@
-from .views import complex_view, fix_dim  # noqa: F401
+from .views import complex_view, fix_dim, window_view  # noqa: F401

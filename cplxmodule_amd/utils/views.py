@@ -1,6 +1,8 @@
 """Strided views into interleaved complex data (cplxmodule/utils/views.py:5-63)."""
 import warnings
 
+import torch
+
 
 def fix_dim(dim, n_dim):
     """non-negative axis index, ValueError when out of range"""
@@ -27,3 +29,24 @@ def complex_view(x, dim=-1, squeeze=True):
     real = even[tuple(index)]
     index[dim] = slice(1, None, 2)
     return real, even[tuple(index)]
+
+
+def window_view(x, dim, size, stride, at=None):
+    """Sliding-window view (cplxmodule/utils/views.py:66-121): like `x.unfold(dim, size, stride)`, but the window
+    dimension of `size` goes to `at` (default: right after `dim`) instead of last.  A pure `as_strided` view: no copy,
+    autograd flows into `x`.  ValueError for size <= 0, stride < 0, an out-of-range dim or a too short x."""
+    if size <= 0:
+        raise ValueError("`size` must be a positive integer.")
+    if stride < 0:
+        raise ValueError("`stride` must be a nonnegative integer.")
+    dim = fix_dim(dim, x.dim())
+    if x.shape[dim] < size:
+        raise ValueError(f"`x` at dim {dim} is too short ({x.shape[dim]}) for this window size ({size}).")
+    at = fix_dim(dim + 1 if at is None else at, x.dim() + 1)
+    shape, strides = list(x.size()), list(x.stride())
+    count = ((shape[dim] - size + 1) + stride - 1) // stride
+    shape_view = shape[:dim] + [count] + shape[dim + 1:]
+    shape_view.insert(at, size)
+    strides_view = strides[:dim] + [strides[dim] * stride] + strides[dim + 1:]
+    strides_view.insert(at, strides[dim])
+    return torch.as_strided(x, shape_view, strides_view)

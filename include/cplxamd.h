@@ -27,7 +27,8 @@ extern "C" {
 
 /* element types of activations / outputs */
 enum { CPLXAMD_F32 = 0, CPLXAMD_BF16 = 1,
-       CPLXAMD_F16 = 2 /* IEEE half: operand type of cplxamd_cgemm_sc_fl / cplxamd_rgemm_sc_fl only */ };
+       CPLXAMD_F16 = 2 /* IEEE half: operand type of cplxamd_cgemm_sc_fl / cplxamd_rgemm_sc_fl only */,
+       CPLXAMD_F64 = 3 /* float64: the Welch spectra (cplxamd_welch_*) only */ };
 
 /* complex product algorithm of cplxamd_cgemm */
 enum {
@@ -891,6 +892,39 @@ int cplxamd_cplx_fn_fwd(const void* z_r, const void* z_i, void* y_r, void* y_i,
                         int64_t n, int fn, int dtype, void* stream);
 int cplxamd_cplx_fn_bwd(const void* z_r, const void* z_i, const void* g_r, const void* g_i,
                         void* dz_r, void* dz_i, int64_t n, int fn, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Welch power spectra (cplxmodule/utils/spectrum.py:7-82 pwelch; csrc/spectrum.hip).  New exports under ABI 25, as the
+ * cplxamd_cplx_fn_* block: nothing existing changes.
+ *   x: `rows` signals of `t` complex samples, sample i of row r at x_r / x_i [r * x_row_stride + i * x_stride] (element
+ *      strides: interleaved complex passes x_i = x_r + 1 and x_stride = 2).  window: n values; segments start every
+ *      `step` samples, S = (t - n) / step + 1 of them.
+ *   pxx[r][k] = sum_s |FFT_n(x_seg(r, s) * window)_k|^2 / (S * scale), scale = fs * sum w^2 (DENSITY) or (sum w)^2
+ *      (SPECTRUM), computed on the device.  Contiguous [rows, n].
+ *   cplxamd_welch_bwd: dx (strided as x, written, not accumulated) of sum_{r,k} g[r][k] pxx[r][k], g contiguous [rows, n]:
+ *      the gradient of the real pair (re, im), dx = 2 / (S scale) sum_s w_j sum_k g_k X_{s,k} e^{+2 pi i j k / n}.
+ * dtype: F32 (x, window, pxx, g, dx float32), BF16 (x and dx bf16, window / pxx / g float32, float32 arithmetic) or
+ * F64.  1 <= n <= CPLXAMD_WELCH_MAX_N.  Deterministic: no atomics, fixed summation orders.
+ * cplxamd_welch_plan is a pure function (no GPU): the path the transform takes (CPLXAMD_WELCH_*) and the workspace
+ * bytes of each direction (nullable outputs); CPLXAMD_EINVAL for n outside [1, CPLXAMD_WELCH_MAX_N] or a bad dtype.
+ * fwd / bwd check every argument before any launch: CPLXAMD_EINVAL (bad value / NULL), CPLXAMD_EWS (workspace smaller
+ * than the plan's), CPLXAMD_ESHAPE (more than 2^31 - 1 workgroups).
+ * ---------------------------------------------------------------------------------- */
+#define CPLXAMD_WELCH_MAX_N (1 << 22)
+enum { CPLXAMD_WELCH_DIRECT = 0,             /* n = 2^k <= 16384 (float32, bf16) / 8192 (float64), in LDS             */
+       CPLXAMD_WELCH_FOURSTEP = 1,           /* n = 2^k above that: four-step N1 x N2 through the workspace             */
+       CPLXAMD_WELCH_BLUESTEIN = 2,          /* other n, M = 2^ceil(log2(2n - 1)) within the LDS limit                  */
+       CPLXAMD_WELCH_BLUESTEIN_FOURSTEP = 3  /* other n, M above it                                                     */ };
+enum { CPLXAMD_WELCH_DENSITY = 0, CPLXAMD_WELCH_SPECTRUM = 1 };
+int cplxamd_welch_plan(int64_t n, int64_t rows, int64_t segments, int dtype, int64_t* ws_fwd_bytes,
+                       int64_t* ws_bwd_bytes);
+int cplxamd_welch_fwd(const void* x_r, const void* x_i, int64_t x_row_stride, int64_t x_stride, int64_t rows, int64_t t,
+                      const void* window, int64_t n, int64_t step, int scaling, double fs, void* pxx, void* ws,
+                      int64_t ws_bytes, int dtype, void* stream);
+int cplxamd_welch_bwd(const void* x_r, const void* x_i, int64_t x_row_stride, int64_t x_stride, int64_t rows, int64_t t,
+                      const void* window, int64_t n, int64_t step, int scaling, double fs, const void* g, void* dx_r,
+                      void* dx_i, int64_t dx_row_stride, int64_t dx_stride, void* ws, int64_t ws_bytes, int dtype,
+                      void* stream);
 
 /* Complex abs-max pooling (cplx.max_poolnd, cplx.py:1114-1175): in every window the element of
  * largest modulus keeps both its parts (first maximum in row-major window order, as torch).
