@@ -179,7 +179,17 @@ SIGNATURES = {
     "cplxamd_welch_plan": [_L, _L, _L, _I, _P, _P],
     "cplxamd_welch_fwd": [_P, _P, _L, _L, _L, _L, _P, _L, _L, _I, _D, _P, _P, _L, _I, _P],
     "cplxamd_welch_bwd": [_P, _P, _L, _L, _L, _L, _P, _L, _L, _I, _D, _P, _P, _P, _L, _L, _P, _L, _I, _P],
+    # still ABI 25: the strided complex contraction behind cplx.einsum (the descriptor is a host struct, EinsumDesc)
+    "cplxamd_ceinsum": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
 }
+
+
+class EinsumDesc(ctypes.Structure):
+    """cplxamd_einsum_desc: groups batch, M, N, K; mode 0 of a group is the outermost."""
+    _fields_ = [("nmodes", ctypes.c_int32 * 4), ("extent", (ctypes.c_int32 * 8) * 4), ("stride_a", (c_int64 * 8) * 4),
+                ("stride_b", (c_int64 * 8) * 4), ("stride_c", (c_int64 * 8) * 4)]
+
+
 # function codes of cplxamd_cplx_fn_fwd / _bwd (CPLXAMD_FN_*)
 CPLX_FN = {"exp": 0, "log": 1, "sin": 2, "cos": 3, "tan": 4, "sinh": 5, "cosh": 6, "tanh": 7}
 _RESTYPES = {"cplxamd_absmax_ws_bytes": c_int64, "cplxamd_conv2d_cl2_mom_chunks": c_int64, "cplxamd_conv2d_cl2_mom_chunks_fl": c_int64, "cplxamd_vd_kl_ws_bytes": c_int64, "cplxamd_lrt_reparam_bwd_cols_ws_bytes": c_int64, "cplxamd_l0_gate_bwd_ws_bytes": c_int64, "cplxamd_bn_ws_bytes": c_int64,

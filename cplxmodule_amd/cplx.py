@@ -325,6 +325,42 @@ def bilinear(input1, input2, weight, bias=None, conjugate=True):
 bilinear_naive = bilinear_cat = bilinear
 
 
+def einsum(equation, *tensors):
+    """Einstein summation of one or two complex tensors, no conjugation (cplxmodule/cplx.py:1032-1059).
+
+    One operand: `torch.einsum` on each plane (a permutation / diagonal / sum is plumbing; any device).  Two operands:
+    everything `torch.einsum` accepts for two operands, as ONE launch of the strided contraction kernel (csrc/einsum.hip;
+    plain `[M, K] x [N, K]` products go to `linear`'s GEMM family: cplxmodule_amd/einsum.py), float32 on the exact
+    float32 matrix instruction whatever `fp32_mode` says, bfloat16 with float32 accumulation, float64 on the checking
+    route of `@`.  Differentiable to any order.  There is no host path: two CPU operands raise."""
+    if not tensors:
+        raise RuntimeError("`einsum()` requires at least one tensor.")
+    if len(tensors) > 2:
+        raise RuntimeError(f"`Cplx.einsum` does not support more than 2 tensors. Got {len(tensors)}.")
+    if len(tensors) == 1:
+        z = tensors[0]
+        return Cplx(torch.einsum(equation, z.real), torch.einsum(equation, z.imag))
+    from . import einsum as _einsum
+    a, b = tensors
+    for pos, t in enumerate((a, b)):
+        if not isinstance(t, Cplx):
+            raise CplxAmdError(f"einsum: operand {pos} is a {type(t).__name__}, not a Cplx (real x complex products are "
+                               "not offered: wrap the tensor in Cplx)")
+    planes = (a.real, a.imag, b.real, b.imag)
+    if any(t.dtype != a.dtype for t in planes):
+        raise CplxAmdError(f"einsum: mixed dtypes {a.real.dtype}/{a.imag.dtype} and {b.real.dtype}/{b.imag.dtype}: "
+                           "both operands must share one dtype")
+    if a.dtype not in (torch.float32, torch.bfloat16, torch.float64):
+        raise CplxAmdError(f"einsum: unsupported dtype {a.dtype}: the contraction kernel takes float32 and bfloat16 "
+                           "(float64 runs the checking route)")
+    if any(not t.is_cuda for t in planes):
+        raise CplxAmdError("einsum: two-operand products run on MI355X only (there is no CPU path): got a tensor on "
+                           f"'{next(t.device for t in planes if not t.is_cuda)}'")
+    if any(t.device != a.device for t in planes):
+        raise CplxAmdError(f"einsum: operands on different devices: {a.device} vs {b.device}")
+    return Cplx(*_einsum.einsum2(equation, *planes))
+
+
 def matmul(u, v):
     """u[..., M, K] @ v[..., K, N]; batch dims of `v` (if any) must equal those of `u`."""
     ur, ui, vr, vi = u.real, u.imag, v.real, v.imag

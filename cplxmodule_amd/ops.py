@@ -4,6 +4,7 @@ Everything here launches libcplxamd.so kernels on the current HIP stream; torch 
 to allocate outputs and to hook the kernels into autograd.  Shapes follow the reference:
 complex tensors are (real, imag) pairs of equal-shaped planes (cplxmodule/cplx.py:10-52).
 """
+import ctypes
 import os
 
 import functools
@@ -11,7 +12,7 @@ import functools
 import torch
 
 from . import _lib, x3
-from ._lib import call, dtype_code, launch_flags, ptr, require_device, scratch_key, stream_ptr, try_call
+from ._lib import CplxAmdError, call, dtype_code, launch_flags, ptr, require_device, scratch_key, stream_ptr, try_call
 
 _ws_cache = {}
 
@@ -316,6 +317,30 @@ def cgemm_batched(ar, ai, a_strides, br, bi, b_strides, batch, M, N, K, conj_b=F
     ci = torch.empty_like(cr)
     call("cplxamd_cgemm_batched", ptr(ar), ptr(ai), *a_strides, ptr(br), ptr(bi), *b_strides, ptr(cr),
          ptr(ci), N, M * N, batch, M, N, K, int(conj_b), dtype_code(ar), dtype_code(cr), stream_ptr())
+    return cr, ci
+
+
+def einsum_desc(plan):
+    """cplxamd_einsum_desc of an einsum.Plan (a host struct: the library copies it into the kernel arguments)."""
+    d = _lib.EinsumDesc()
+    for g, modes in enumerate(plan.groups):
+        if len(modes) > 8:
+            raise CplxAmdError("einsum: more than 8 modes in a group")
+        d.nmodes[g] = len(modes)
+        for i, md in enumerate(modes):
+            d.extent[g][i], d.stride_a[g][i], d.stride_b[g][i], d.stride_c[g][i] = md.extent, md.sa, md.sb, md.sc
+    return d
+
+
+def ceinsum(ar, ai, br, bi, plan):
+    """C = contraction of op(A) and op(B) as `plan` (cplxmodule_amd.einsum.Plan) says, in ONE launch; C is allocated
+    contiguous in the plan's output order."""
+    require_device(ar, ai, br, bi)
+    cr = torch.empty(plan.out_shape, dtype=ar.dtype, device=ar.device)
+    ci = torch.empty_like(cr)
+    d = einsum_desc(plan)
+    call("cplxamd_ceinsum", ptr(ar), ptr(ai), ptr(br), ptr(bi), ptr(cr), ptr(ci), ctypes.byref(d), int(plan.conj_a),
+         int(plan.conj_b), dtype_code(ar), dtype_code(cr), stream_ptr())
     return cr, ci
 
 

@@ -926,6 +926,36 @@ int cplxamd_welch_bwd(const void* x_r, const void* x_i, int64_t x_row_stride, in
                       void* dx_i, int64_t dx_row_stride, int64_t dx_stride, void* ws, int64_t ws_bytes, int dtype,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Strided complex tensor contraction (cplx.einsum with two operands, cplxmodule/cplx.py:1032-1059; csrc/einsum.hip).  A new
+ * export under ABI 25: nothing existing changes.
+ *   C[b.., m.., n..] = sum_{k..} op(A)[b.., m.., k..] * op(B)[b.., n.., k..],   op = identity or conjugate per operand
+ * on planar re / im operands.  The four index groups (CPLXAMD_EINSUM_BATCH / _M / _N / _K) are lists of up to
+ * CPLXAMD_EINSUM_MAX_MODES modes; mode 0 of a group is the outermost, the last one runs fastest.  A mode is an extent and
+ * its ELEMENT stride in A, B and C (stride_a of an N mode, stride_b of an M mode and stride_c of a K mode are not read).
+ * nmodes == 0 stands for one mode of extent 1.  Strides may be zero (broadcast) or negative in A and B; a C stride of a
+ * mode of extent > 1 must not be zero.  Every extent and the product of the extents of a group must fit 31 bits.
+ * in_dtype = out_dtype = CPLXAMD_F32 (v_mfma_f32_32x32x2_f32: an fmaf chain in k order) or CPLXAMD_BF16
+ * (v_mfma_f32_32x32x16_bf16, float32 accumulation, one rounding on store).  The descriptor is a HOST struct and is copied
+ * into the kernel arguments: one launch, no workspace, no device-side table, no synchronisation (capturable); no atomics,
+ * the same inputs give the same bits.  Any base-pointer alignment and any strides are taken; 16-byte loads are used per
+ * operand when the innermost K mode has stride 1 and the base pointer, the other strides and that extent allow it.
+ * Checked before any GPU call: NULL pointer, nmodes outside [0, 8], negative extent, zero C stride -> CPLXAMD_EINVAL;
+ * a dtype other than F32 / BF16 or in_dtype != out_dtype, a group or the grid beyond 2^31 - 1 -> CPLXAMD_ESHAPE; an
+ * empty result (an extent 0 among batch / M / N) -> 0 without a launch; an empty K group writes zeros.
+ * ---------------------------------------------------------------------------------- */
+#define CPLXAMD_EINSUM_MAX_MODES 8
+enum { CPLXAMD_EINSUM_BATCH = 0, CPLXAMD_EINSUM_M = 1, CPLXAMD_EINSUM_N = 2, CPLXAMD_EINSUM_K = 3 };
+typedef struct cplxamd_einsum_desc {
+  int32_t nmodes[4];
+  int32_t extent[4][CPLXAMD_EINSUM_MAX_MODES];
+  int64_t stride_a[4][CPLXAMD_EINSUM_MAX_MODES];
+  int64_t stride_b[4][CPLXAMD_EINSUM_MAX_MODES];
+  int64_t stride_c[4][CPLXAMD_EINSUM_MAX_MODES];
+} cplxamd_einsum_desc;   /* 912 bytes */
+int cplxamd_ceinsum(const void* a_r, const void* a_i, const void* b_r, const void* b_i, void* c_r, void* c_i,
+                    const cplxamd_einsum_desc* d, int conj_a, int conj_b, int in_dtype, int out_dtype, void* stream);
+
 /* Complex abs-max pooling (cplx.max_poolnd, cplx.py:1114-1175): in every window the element of
  * largest modulus keeps both its parts (first maximum in row-major window order, as torch).
  * pool = int[14]: B, C, H, W, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw.  idx: int32 [B, C, Ho, Wo],
