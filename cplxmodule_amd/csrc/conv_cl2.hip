@@ -504,9 +504,19 @@ __global__ __launch_bounds__(NT) void conv_cl2_kernel(Args g) {
   // and a second, column-wise read of the staged bf16 rows: lane = (channel pair cp = lane & 31, row group rg = lane >> 5),
   // 8 rows x 2 planes x 4 bytes -- the two row groups take rows of opposite parity in every read, i.e. opposite halves of
   // the 64 banks (the row pitch is half of them; within a row the XOR swizzle keeps the 32 channel pairs on 32 banks).
-  // Ten per-lane sums live through the persistent loop; pixels outside the image contribute zeros.
+  // Ten per-lane float32 sums live through the persistent loop -- of the values MINUS A PIVOT, the first in-image value
+  // pair the lane meets for each of its two channels (kept as the stored bf16 bits): raw float32 sums of x^2 over the
+  // hundreds of pixels a lane carries lose the variance to the mean (at 512 pixels per lane the layer's statistics came
+  // out 3e-5 off at mean / std 8 and 4e-5 at 32, against the 2e-5 the pair is held to), sums about a value from the data are those of a mean / std ~ 1 problem whatever the bias or the
+  // input mean is.  The raw moments the partial rows promise are put back together per lane in double after the loop.
+  // Pixels outside the image contribute the pivot itself, i.e. zeros to the shifted sums, and do not count in m_n.
   typedef float f2v __attribute__((ext_vector_type(2)));
   f2v m_r = {0.f, 0.f}, m_i = {0.f, 0.f}, m_rr = {0.f, 0.f}, m_ii = {0.f, 0.f}, m_ri = {0.f, 0.f};
+  uint32_t piv_r = 0u, piv_i = 0u;
+  int m_n = 0;                                             // in-image pixels in this lane's sums
+  auto unpack2 = [](uint32_t d) __attribute__((always_inline)) -> f2v {
+    return f2v{__uint_as_float(d << 16), __uint_as_float(d & 0xffff0000u)};
+  };
   auto epilogue_mom = [&]() __attribute__((always_inline)) {
     const int t = opaque_tid();
     const int ln = t & 63, w_ = t >> 6, q31 = ln & 31, qk = ln >> 5;
@@ -520,9 +530,8 @@ __global__ __launch_bounds__(NT) void conv_cl2_kernel(Args g) {
     // is an XOR of a lane part and a k part, and the fields do not overlap: offset = lane part ^ (k << 7 | k << 3)
     const uint32_t mbase = (uint32_t)((rg << 10) ^ (rg << 7) ^ ((((cp >> 1) ^ (rg << 3) ^ rg) & 15) << 3) ^ ((cp & 1) << 2));
     const bool interior = __builtin_amdgcn_readfirstlane((int)(tc.x0 + TW <= g.Wo && tc.y0 + TH <= g.Ho)) != 0;
-    auto moments_of = [&](uint32_t dr, uint32_t di) __attribute__((always_inline)) {
-      const f2v R = {__uint_as_float(dr << 16), __uint_as_float(dr & 0xffff0000u)};
-      const f2v I = {__uint_as_float(di << 16), __uint_as_float(di & 0xffff0000u)};
+    auto moments_of = [&](uint32_t dr, uint32_t di, f2v P_r, f2v P_i) __attribute__((always_inline)) {
+      const f2v R = unpack2(dr) - P_r, I = unpack2(di) - P_i;
       m_r += R; m_i += I;
       m_rr += R * R; m_ii += I * I; m_ri += R * I;
     };
@@ -585,14 +594,21 @@ __global__ __launch_bounds__(NT) void conv_cl2_kernel(Args g) {
         }
         __builtin_amdgcn_sched_barrier(0);
         if (rowin) {
+          // this lane's eight pixels are columns c0 + (k ^ rg): the nv of them inside the image are a prefix, and the
+          // first one (read k = rg) becomes the pivot if the lane has none yet
+          const int c0 = tc.x0 + half * 16 + 8 * rg;
+          const int nv = interior ? 8 : min(max(g.Wo - c0, 0), 8);
+          if (m_n == 0 && nv > 0) { piv_r = rg ? dr[1] : dr[0]; piv_i = rg ? di[1] : di[0]; }
+          m_n += nv;
+          const f2v P_r = unpack2(piv_r), P_i = unpack2(piv_i);
           if (interior) {                                        // (scalar branch: most tiles)
 #pragma unroll
-            for (int k = 0; k < 8; ++k) moments_of(dr[k], di[k]);
+            for (int k = 0; k < 8; ++k) moments_of(dr[k], di[k], P_r, P_i);
           } else {
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-              const bool ok = tc.x0 + half * 16 + 8 * rg + (k ^ rg) < g.Wo;
-              moments_of(ok ? dr[k] : 0u, ok ? di[k] : 0u);
+              const bool ok = (k ^ rg) < nv;
+              moments_of(ok ? dr[k] : piv_r, ok ? di[k] : piv_i, P_r, P_i);
             }
           }
         }
@@ -694,14 +710,27 @@ __global__ __launch_bounds__(NT) void conv_cl2_kernel(Args g) {
   }
   wait_vmcnt<0>();
   if constexpr (MOM) {
-    // per workgroup: row groups (lane ^ 32), then the eight waves through LDS (the rings are idle: nothing in flight)
+    // per lane: the raw moments from the sums about the pivot (p, q), in double -- sum x = s + n p, sum x^2 = ss + 2 p s +
+    // n p^2, sum x y = sxy + q sx + p sy + n p q; then per workgroup: row groups (lane ^ 32) and the eight waves through LDS
+    // (the rings are idle: nothing in flight), all in double
     const int t = opaque_tid();
     const int ln = t & 63, w_ = t >> 6, cp = ln & 31;
-    float vals[10] = {m_r.x, m_r.y, m_i.x, m_i.y, m_rr.x, m_rr.y, m_ii.x, m_ii.y, m_ri.x, m_ri.y};
+    const f2v P_r = unpack2(piv_r), P_i = unpack2(piv_i);
+    const double n = (double)m_n;
+    double vals[10];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const double p = P_r[e], q = P_i[e], sr = m_r[e], si = m_i[e];
+      vals[0 + e] = sr + n * p;
+      vals[2 + e] = si + n * q;
+      vals[4 + e] = (double)m_rr[e] + 2.0 * p * sr + n * p * p;
+      vals[6 + e] = (double)m_ii[e] + 2.0 * q * si + n * q * q;
+      vals[8 + e] = (double)m_ri[e] + q * sr + p * si + n * p * q;
+    }
 #pragma unroll
     for (int k = 0; k < 10; ++k) vals[k] += __shfl_xor(vals[k], 32);
     __builtin_amdgcn_s_barrier();
-    float* red = reinterpret_cast<float*>(smem);
+    double* red = reinterpret_cast<double*>(smem);
     if (ln < 32) {
 #pragma unroll
       for (int k = 0; k < 10; ++k) red[(w_ * 32 + cp) * 10 + k] = vals[k];
@@ -711,7 +740,7 @@ __global__ __launch_bounds__(NT) void conv_cl2_kernel(Args g) {
       const int ch = t & (BN - 1), k = t / BN;
       double sum = 0.0;
 #pragma unroll
-      for (int w = 0; w < NT / 64; ++w) sum += (double)red[(w * 32 + (ch >> 1)) * 10 + 2 * k + (ch & 1)];
+      for (int w = 0; w < NT / 64; ++w) sum += red[(w * 32 + (ch >> 1)) * 10 + 2 * k + (ch & 1)];
       // (the row was zeroed by the launcher: the other column tiles' channels of this workgroup's row stay 0)
       g.mom[((int64_t)blockIdx.x * g.Cout + tc.nt * BN + ch) * 5 + k] = sum;
     }

@@ -105,6 +105,16 @@ def test_batchnorm_vs_oracle_shapes(shape):
         # statistics, ~1e-7.  (The 3.4-4.2e-5 that profiles/r03_parity_report.txt shows for this test is the whitening
         # check further down: E|z|^2 = 1 - eps / V with eps = 1e-5 -- a property of the layer, not an error.)
         np.testing.assert_allclose(N(t), bw[n], **_tol(bw[n], 1e-5), err_msg=n)
+    # the same comparisons per feature, norm-wise (||got_f - ref_f|| / ||ref_f||): a feature of small scale is not hidden
+    # behind the tensor's max |ref|
+    import bn_stress_cases as sc
+    per_feature = {"y": (sc.stack_planes(N(y.real), N(y.imag)), sc.stack_planes(yr, yi)),
+                   "dx": (sc.stack_planes(N(txr.grad), N(txi.grad)), sc.stack_planes(bw["dxr"], bw["dxi"])),
+                   "dweight": (N(bn.weight.grad).reshape(4, -1), bw["dweight"].reshape(4, -1)),
+                   "dbias": (N(bn.bias.grad), bw["dbias"])}
+    for n, (got, ref) in per_feature.items():
+        e = sc.rel_per_feature(got, ref)
+        np.testing.assert_allclose(1.0 + e, np.ones_like(e), rtol=2e-5 if n == "y" else 1e-5, atol=0, err_msg=n + " per feature")
     # whitening property without affine
     bn2 = cls(F_, affine=False).to("cuda")
     z = bn2(Cplx(T(xr), T(xi)))

@@ -148,6 +148,11 @@ def test_bias_gradient_from_batchnorm_backward_sums(monkeypatch):
     # (the layer's own apply pass: with the apply folded into the weight gradient -- round 6, tests/test_gpu_bn_fold.py -- the
     #  sums come from the reduce pass analytically, i.e. without the rounding noise of the stored bf16 values)
     monkeypatch.setattr(cv, "_BN_FOLD", False)
+    # (and the layer's own moment pass in BOTH runs: the first step arms the convolution, so the second would take its
+    #  statistics from the convolution's epilogue -- the two routes agree to ~1e-7, which may move one stored bf16 dX entry by
+    #  a step, as test_conv_batchnorm_pair_uses_the_epilogue_moments allows, and that step, 2^-7, would land in the sum
+    #  compared here.  What is under test is the hand-over of the sums, on identical dX.)
+    monkeypatch.setattr(cv, "_MOMENTS", False)
     torch.manual_seed(3)
     dev = "cuda"
     conv_, bn = nn.CplxConv2d(64, 64, 3, padding=1).to(dev), nn.CplxBatchNorm2d(64).to(dev)

@@ -251,6 +251,14 @@ def test_conv_epilogue_moments_match_a_pass_over_the_output(B, C, H, W, pad, Nc)
     scale = np.abs(ref).max(0, keepdims=True)
     np.testing.assert_allclose(got, ref, rtol=0, atol=2e-6 * scale.max())
     np.testing.assert_allclose(got / scale, ref / scale, rtol=0, atol=1e-5)
+    # the CENTRAL second moments, which is what the batch-norm layer forms from them (E x^2 - (E x)^2: the raw ones above
+    # hide a cancellation), per channel, against the same expression on the float64 sums of the stored output
+    n = float(r.shape[1])
+    central = lambda m: np.stack([m[:, 2] / n - (m[:, 0] / n) ** 2, m[:, 3] / n - (m[:, 1] / n) ** 2,  # noqa: E731
+                                  m[:, 4] / n - m[:, 0] * m[:, 1] / n ** 2], 1)
+    cg, cr = central(got), central(ref)
+    var = np.sqrt(cr[:, 0] * cr[:, 1])[:, None]
+    np.testing.assert_allclose(cg / var, cr / var, rtol=2e-5, atol=2e-6)
     # a modified output no longer carries them
     yr.add_(1)
     assert ops.moments_hint(yr, yi) is None
