@@ -181,7 +181,15 @@ SIGNATURES = {
     "cplxamd_welch_bwd": [_P, _P, _L, _L, _L, _L, _P, _L, _L, _I, _D, _P, _P, _P, _L, _L, _P, _L, _I, _P],
     # still ABI 25: the strided complex contraction behind cplx.einsum (the descriptor is a host struct, EinsumDesc)
     "cplxamd_ceinsum": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    # still ABI 25: the finishing kernels of the semi-unitary initialiser (nn/init.py; F64 is a plane dtype here)
+    "cplxamd_init_ws_bytes": [],
+    "cplxamd_init_moments": [_P, _P, _L, _I, _P, _P, _P],
+    "cplxamd_init_ns_poly": [_P, _P, _P, _P, _I, _D, _D, _I, _P, _P, _P],
+    "cplxamd_init_scale_store": [_P, _P, _P, _P, _L, _L, _I, _I, _D, _P, _P, _I, _I, _P],
 }
+
+# modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
+INIT_SCALE_NORM, INIT_SCALE_STD, INIT_SCALE_CONST = 0, 1, 2
 
 
 class EinsumDesc(ctypes.Structure):
@@ -192,7 +200,7 @@ class EinsumDesc(ctypes.Structure):
 
 # function codes of cplxamd_cplx_fn_fwd / _bwd (CPLXAMD_FN_*)
 CPLX_FN = {"exp": 0, "log": 1, "sin": 2, "cos": 3, "tan": 4, "sinh": 5, "cosh": 6, "tanh": 7}
-_RESTYPES = {"cplxamd_absmax_ws_bytes": c_int64, "cplxamd_conv2d_cl2_mom_chunks": c_int64, "cplxamd_conv2d_cl2_mom_chunks_fl": c_int64, "cplxamd_vd_kl_ws_bytes": c_int64, "cplxamd_lrt_reparam_bwd_cols_ws_bytes": c_int64, "cplxamd_l0_gate_bwd_ws_bytes": c_int64, "cplxamd_bn_ws_bytes": c_int64,
+_RESTYPES = {"cplxamd_absmax_ws_bytes": c_int64, "cplxamd_init_ws_bytes": c_int64, "cplxamd_conv2d_cl2_mom_chunks": c_int64, "cplxamd_conv2d_cl2_mom_chunks_fl": c_int64, "cplxamd_vd_kl_ws_bytes": c_int64, "cplxamd_lrt_reparam_bwd_cols_ws_bytes": c_int64, "cplxamd_l0_gate_bwd_ws_bytes": c_int64, "cplxamd_bn_ws_bytes": c_int64,
              "cplxamd_conv2d_wgrad_ws_bytes": c_int64, "cplxamd_conv2d_bf16_wgrad_ws_bytes": c_int64, "cplxamd_colsum_ws_bytes": c_int64, "cplxamd_gemm_ws_bytes": c_int64,
              "cplxamd_cgemm3m_ws_bytes": c_int64,
              "cplxamd_conv2d_nhwc_wgrad_ws_bytes": c_int64,

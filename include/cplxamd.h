@@ -28,7 +28,7 @@ extern "C" {
 /* element types of activations / outputs */
 enum { CPLXAMD_F32 = 0, CPLXAMD_BF16 = 1,
        CPLXAMD_F16 = 2 /* IEEE half: operand type of cplxamd_cgemm_sc_fl / cplxamd_rgemm_sc_fl only */,
-       CPLXAMD_F64 = 3 /* float64: the Welch spectra (cplxamd_welch_*) only */ };
+       CPLXAMD_F64 = 3 /* float64: the Welch spectra (cplxamd_welch_*) and the initialiser kernels (cplxamd_init_*) only */ };
 
 /* complex product algorithm of cplxamd_cgemm */
 enum {
@@ -1006,6 +1006,39 @@ int cplxamd_gemm_f64(const double* a_r, const double* a_i, int64_t a_rs, int64_t
 int cplxamd_conv2d_f64(const double* p_r, const double* p_i, const double* q_r, const double* q_i, const double* bias_r,
                        const double* bias_i, double* out_r, double* out_i, const int* geom, int mode, void* stream);
 int cplxamd_expi_f64(const double* x, double* y, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Finishing kernels of the semi-unitary initialiser (cplx_trabelsi_independent_, cplxmodule/nn/init.py:90-123; csrc/
+ * init.hip).  New exports under ABI 25: nothing existing changes.  The unitary polar factor of a random matrix comes from
+ * the Newton-Schulz recurrence X <- X (1.5 I - 0.5 X^H X) on cplxamd_cgemm_fl / cplxamd_gemm_f64; these three passes are
+ * what is left around the two GEMMs of a step.  Planes are dense, dtype = CPLXAMD_F32 or CPLXAMD_F64 (the arithmetic of
+ * the iteration); sums are float64, reduced in a fixed order through `ws` (cplxamd_init_ws_bytes() bytes, 8-byte aligned):
+ * the same input gives the same bits, no atomics.
+ *   cplxamd_init_moments      out[0..2] = sum re, sum im, sum (re^2 + im^2) over n elements (device float64[3]).
+ *   cplxamd_init_ns_poly      P = a I + b G on the k x k planes of G (one fma on the diagonal, one product elsewhere, in
+ *                             the planes' arithmetic) and *resid2 = ||G - I||_F^2 (device float64).
+ *   cplxamd_init_scale_store  out = in * f on [rows, cols] planes, or with transpose != 0 the hermitian transpose
+ *                             out[c][r] = conj(in[r][c]) * f ([cols, rows]); the float64 product is rounded ONCE to
+ *                             out_dtype: F32 or BF16 for F32 planes, F64 for F64 planes (the casts a parameter needs;
+ *                             any other pair: CPLXAMD_EINVAL).  f is derived ON THE DEVICE from moments[0..2] (device float64,
+ *                             as cplxamd_init_moments writes them; n = rows * cols):
+ *                               CPLXAMD_INIT_SCALE_NORM   f = target / sqrt(m2)                       (1 / ||in||_F)
+ *                               CPLXAMD_INIT_SCALE_STD    f = target / sqrt(m2 / n - |m0 + i m1|^2 / n^2)   (std -> target)
+ *                               CPLXAMD_INIT_SCALE_CONST  f = target (moments not read, may be NULL)
+ *                             The launcher cannot know a device value, so a bad factor is reported on the device: when the
+ *                             radicand is 0, negative or not finite (or f is not finite) NOTHING is stored and *status
+ *                             (device float64, nullable) is set to 1, else to 0 -- never an infinite or NaN output.
+ * Checked before any launch (CPLXAMD_EINVAL): NULL planes / outputs / ws, n <= 0, k <= 0, rows or cols <= 0, a plane dtype
+ * other than F32 / F64, an unknown out_dtype or mode, a NaN target; more than 2^31 - 1 tiles: CPLXAMD_ESHAPE.
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_INIT_SCALE_NORM = 0, CPLXAMD_INIT_SCALE_STD = 1, CPLXAMD_INIT_SCALE_CONST = 2 };
+int64_t cplxamd_init_ws_bytes(void);
+int cplxamd_init_moments(const void* re, const void* im, int64_t n, int dtype, double* out, void* ws, void* stream);
+int cplxamd_init_ns_poly(const void* g_r, const void* g_i, void* p_r, void* p_i, int k, double a, double b, int dtype,
+                         double* resid2, void* ws, void* stream);
+int cplxamd_init_scale_store(const void* in_r, const void* in_i, void* out_r, void* out_i, int64_t rows, int64_t cols,
+                             int transpose, int mode, double target, const double* moments, double* status, int in_dtype,
+                             int out_dtype, void* stream);
 
 #ifdef __cplusplus
 }
