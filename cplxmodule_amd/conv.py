@@ -153,7 +153,7 @@ def grad_grid(gr, gi, geom):
 # ---- channels-last end to end (csrc/conv_cl.hip): 3 x 3-style "same" convolutions, stride 1, groups 1 -------- #
 _CL_FORCE = False            # tests: take the kernels on tiny shapes too
 _CL_ENABLED = True
-_CL_PATCH = os.environ.get("CPLXAMD_CL_PATCH", "1") != "0"      # conv_cl2.hip where it applies (A/B: set to 0)
+_CL_PATCH = True      # conv_cl2.hip where it applies (False: the row kernel conv_cl.hip; the tests compare the two)
 _CL_MIN_FLOP = 4e9
 
 
@@ -389,7 +389,7 @@ def cl_conv(xr, xi, wr, wi, br, bi, geom, dgrad=False, moments=False):
     return yr, yi
 
 
-_LRT_DX_FUSE = os.environ.get("CPLXAMD_LRT_DX_FUSE", "1") != "0"      # (A/B: set to 0 for the two launches)
+_LRT_DX_FUSE = True      # (False: the two launches, bit-identical; the tests compare the two)
 
 
 def cl_conv_lrt_dx(gr, gi, wr, wi, geom, xr, xi, ga):
@@ -698,13 +698,9 @@ def _rows(t):
     return t.permute(0, 2, 3, 1).reshape(B * H * W, C)
 
 
-_X2_ONE_LAUNCH = os.environ.get("CPLXAMD_X2_ONE", "1") != "0"    # (A/B: 0 = the two launches of the first x2 form)
-
-
 def _x2_weight_packs(wr, wi, dgrad):
-    """Packed LDS images of the weights, and the weights' scale.  One launch (the contraction window wraps around the
-    [h1|h0] pixel as [h0|h1|h0]): (None, pack of [w1|w0|w0] -- 3 C channels --, scale); two launches: (pack of w1 -- C
-    channels --, pack of [w0|w0] -- 2 C channels --, scale)."""
+    """Packed LDS image of the weights [w1|w0|w0] -- 3 C channels: the contraction window wraps around the [h1|h0] pixel
+    as [h0|h1|h0] --, and the weights' scale."""
     from . import x3
     Co, Ci, KH, KW = wr.shape
     pr, pi = x3.split_planes((wr.reshape(Co, -1), wi.reshape(Co, -1)), kind="x2")          # [Co, 2 Ci 9] = [h1|h0]
@@ -712,12 +708,7 @@ def _x2_weight_packs(wr, wi, dgrad):
     cut = lambda p: (p.t[:, :n].reshape(Co, Ci, KH, KW), p.t[:, n:].reshape(Co, Ci, KH, KW))  # noqa: E731  (w1, w0)
     (w1r, w0r), (w1i, w0i) = cut(pr), cut(pi)
     cat = 0 if dgrad else 1                            # the contraction channels: Co for the data gradient, Ci forward
-    if _X2_ONE_LAUNCH:
-        return None, _cl_pack(torch.cat([w1r, w0r, w0r], cat).contiguous(), torch.cat([w1i, w0i, w0i], cat).contiguous(),
-                              dgrad), pr.scale
-    small = _cl_pack(w1r.contiguous(), w1i.contiguous(), dgrad)
-    big = _cl_pack(torch.cat([w0r, w0r], cat).contiguous(), torch.cat([w0i, w0i], cat).contiguous(), dgrad)
-    return small, big, pr.scale
+    return _cl_pack(torch.cat([w1r, w0r, w0r], cat).contiguous(), torch.cat([w1i, w0i, w0i], cat).contiguous(), dgrad), pr.scale
 
 
 def _x2_conv(pieces, wr, wi, br, bi, geom, dgrad):
@@ -732,7 +723,7 @@ def _x2_conv(pieces, wr, wi, br, bi, geom, dgrad):
     dev = pr.t.device
     yr = torch.empty(oshape, dtype=torch.float32, device=dev, memory_format=torch.channels_last)
     yi = torch.empty_like(yr)
-    small, big, wscale = _x2_weight_packs(wr, wi, dgrad)
+    pack, wscale = _x2_weight_packs(wr, wi, dgrad)
     ws = _scratch(dev, int(_lib.load().cplxamd_conv2d_cl_ws_bytes(N)))
     flags = launch_flags()
     per = Hin * Win * 2 * C * 2                                   # bytes of one image of pieces
@@ -745,17 +736,9 @@ def _x2_conv(pieces, wr, wi, br, bi, geom, dgrad):
         xi_ = pi.t[b0 * Hin * Win:]
         o_r = yr.permute(0, 2, 3, 1).reshape(-1)[b0 * opix:]
         o_i = yi.permute(0, 2, 3, 1).reshape(-1)[b0 * opix:]
-        if small is None:
-            # one launch: the window [h0|h1|h0] (starts C channels into the [h1|h0] pixel, wraps) * [w1|w0|w0] (+ bias)
-            call("cplxamd_conv2d_cl2h_wrap_fl", ptr(xr_), ptr(xi_), 2 * C, C, ptr(big), ptr(br), ptr(bi), ptr(o_r), ptr(o_i), 0,
-                 ptr(pr.scale), ptr(wscale), nb, H, W, 3 * C, N, ph, pw, int(dgrad), ptr(ws), ws.numel(), flags, stream_ptr())
-            continue
-        # launch 1: h0 (the second half of every row) * w1 (+ bias); launch 2: [h1|h0] * [w0|w0], accumulated
-        h0r, h0i = xr_.reshape(-1)[C:], xi_.reshape(-1)[C:]
-        call("cplxamd_conv2d_cl2h_fl", ptr(h0r), ptr(h0i), 2 * C, ptr(small), ptr(br), ptr(bi), ptr(o_r), ptr(o_i), 0,
-             ptr(pr.scale), ptr(wscale), nb, H, W, C, N, ph, pw, int(dgrad), ptr(ws), ws.numel(), flags, stream_ptr())
-        call("cplxamd_conv2d_cl2h_fl", ptr(xr_), ptr(xi_), 2 * C, ptr(big), None, None, ptr(o_r), ptr(o_i), 1,
-             ptr(pr.scale), ptr(wscale), nb, H, W, 2 * C, N, ph, pw, int(dgrad), ptr(ws), ws.numel(), flags, stream_ptr())
+        # one launch: the window [h0|h1|h0] (starts C channels into the [h1|h0] pixel, wraps) * [w1|w0|w0] (+ bias)
+        call("cplxamd_conv2d_cl2h_wrap_fl", ptr(xr_), ptr(xi_), 2 * C, C, ptr(pack), ptr(br), ptr(bi), ptr(o_r), ptr(o_i), 0,
+             ptr(pr.scale), ptr(wscale), nb, H, W, 3 * C, N, ph, pw, int(dgrad), ptr(ws), ws.numel(), flags, stream_ptr())
     return yr, yi
 
 

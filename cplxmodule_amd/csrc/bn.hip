@@ -20,14 +20,10 @@ constexpr int kFwdCoef = 8;  // mu, mv, a00, a01, a10, a11, b0, b1
 constexpr int kBwdCoef = kBnBwdCoef; // mu, mv, e00, e01, e10, e11, cuu, cuv, cvv, ku, kv, pad
 
 // The channels-last row kernels stream planes of gigabytes, every byte touched once per pass: nontemporal accesses for
-// the bf16 planes (bit 0: stores, bit 1: loads), as in kl.hip: forward -4 %, backward -4 % same box.
-#ifndef BN_NT
-#define BN_NT 3
-#endif
+// the bf16 planes, as in kl.hip: forward -4 %, backward -4 % same box.
 typedef uint32_t u32x4_nt __attribute__((ext_vector_type(4)));
 typedef float f32x4_nt __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f8 ld8s(const bf16_t* p) {
-#if BN_NT & 2
   const u32x4_nt t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_nt*>(p));
   f8 r;
 #pragma unroll
@@ -36,21 +32,14 @@ __device__ __forceinline__ f8 ld8s(const bf16_t* p) {
     r.h[e >> 1].v[(e & 1) * 2 + 1] = __uint_as_float(t[e] & 0xffff0000u);
   }
   return r;
-#else
-  return ld8(p);
-#endif
 }
 // (float32 planes: plain accesses -- nontemporal ones cost the backward 25 % on the same box, scripts/r06/bn_nt_ab.py)
 __device__ __forceinline__ f8 ld8s(const float* p) { return ld8(p); }
 __device__ __forceinline__ void st8s(bf16_t* p, const f8& a) {
-#if BN_NT & 1
   u32x4_nt w;
 #pragma unroll
   for (int e = 0; e < 4; ++e) w[e] = pack_bf16(a.h[e >> 1].v[(e & 1) * 2], a.h[e >> 1].v[(e & 1) * 2 + 1]);
   __builtin_nontemporal_store(w, reinterpret_cast<u32x4_nt*>(p));
-#else
-  st8(p, a);
-#endif
 }
 __device__ __forceinline__ void st8s(float* p, const f8& a) { st8(p, a); }
 

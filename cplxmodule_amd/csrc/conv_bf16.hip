@@ -20,11 +20,10 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "prims.h"
 
 namespace cplxamd {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int FBM = 64, FBN = 64, FBK = 32, FROW = 80;   // FROW: LDS row pitch in bytes
 constexpr int FPLANE = FBM * FROW;                       // 5120 B per operand plane

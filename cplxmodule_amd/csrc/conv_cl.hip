@@ -23,30 +23,19 @@
 //    stages later.
 //  * weights are pre-packed per (output-channel tile, stage) as the LDS image itself (csrc: pack_kernel), with
 //    the conjugate / flip / channel swap of the data gradient folded into the packing, so the kernel has one form.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "common.h"
+#include "prims.h"
 #include "launch.h"   // per-call launch policy (CPLXAMD_LAUNCH_SHARED: the chip is shared with collectives)
 
 namespace cplxamd {
 namespace cl {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int NT = 512, TM = 512, BN = 64;
 constexpr int A_PLANE = TM * 32 + 64;        // 512 rows x 16 channels, then the zero row (row 512)
 constexpr int ZROW = TM * 32;                // plane-relative byte address of the zero row
-// ablation builds (-DCPLXAMD_CL_DBG=n, timing only): 1 no global stores, 2 every store goes to the dump rows
-// (L2-resident), 4 no epilogue at all, 8 no LDS-DMA after the prologue, 16 no start stagger, 32 contiguous A source
-#ifndef CPLXAMD_CL_DBG
-#define CPLXAMD_CL_DBG 0
-#endif
-constexpr int kClDbg = CPLXAMD_CL_DBG;
-constexpr int NST = (kClDbg & 5) ? 0 : 16;   // global stores per wave in the epilogue (2 planes x 2 blocks x 4 rounds)
+constexpr int NST = 16;                       // global stores per wave in the epilogue (2 planes x 2 blocks x 4 rounds)
 
 template <int KW> struct Geo {
   static constexpr int W_PLANE = KW * 64 * 32;                 // [kw][64 co][16 ch] bf16
@@ -59,8 +48,6 @@ template <int KW> struct Geo {
   static constexpr int DUMP = EPI + 8 * EPI_WAVE;              // where the surplus half of a weight piece goes
   static constexpr int SMEM = DUMP + 4096;
 };
-
-struct FastDiv { uint32_t m; int s; };       // n / d for any 32-bit n (round-up method); d == 1: s < 0
 
 struct Args {
   const void* x_r; const void* x_i;          // [P][C] bf16
@@ -76,44 +63,6 @@ struct Args {
   FastDiv div_w, div_h;
   int stagger, stagger_from;                 // start delay: (blockIdx - stagger_from) * stagger clocks (0 below stagger_from)
 };
-
-__device__ __forceinline__ uint32_t fast_div(uint32_t n, FastDiv d) {
-  if (d.s < 0) return n;
-  const uint32_t t = __umulhi(d.m, n);
-  return (t + ((n - t) >> 1)) >> d.s;
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ bf16x8 neg_frag(bf16x8 v) {
-  uint4 u = __builtin_bit_cast(uint4, v);
-  u.x ^= 0x80008000u; u.y ^= 0x80008000u; u.z ^= 0x80008000u; u.w ^= 0x80008000u;
-  return __builtin_bit_cast(bf16x8, u);
-}
-
-// LDS-DMA through a buffer descriptor: lane data = 16 bytes at  base + voff + soff, zeros when that is outside
-// [0, num_records) (voff wraps in 32 bits, so a "negative" row is out of range too); destination M0 + lane * 16.
-__device__ __forceinline__ void buf_lds16(i32x4 rsrc, uint32_t voff, uint32_t soff_uniform, uint32_t lds_off_uniform) {
-#if defined(__HIP_DEVICE_COMPILE__)
-#ifndef CPLXAMD_CL_DMA_MOD
-#define CPLXAMD_CL_DMA_MOD ""
-#endif
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen " CPLXAMD_CL_DMA_MOD " lds"
-               :
-               : "v"(voff), "s"(rsrc), "s"(lds_off_uniform), "s"(soff_uniform)
-               : "memory");
-#endif
-}
-
-__device__ __forceinline__ i32x4 make_rsrc(const void* base, uint32_t bytes) {
-  const uint64_t a = (uint64_t)(uintptr_t)base;
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
-  const uint32_t nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)bytes);
-  return i32x4{(int)lo, (int)(hi & 0xffffu), (int)nb, 0x00020000};
-}
 
 enum { FL_NORMAL = 0, FL_FIRST0 = 1, FL_LAST = 2, FL_FIRST1 = 3 };
 
@@ -149,8 +98,7 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
 
   const i32x4 rs_xr = make_rsrc(g.x_r, g.x_bytes), rs_xi = make_rsrc(g.x_i, g.x_bytes);
   const i32x4 rs_w = make_rsrc(g.w, g.w_bytes);
-  // (ablation bit 32: rows of the source read as if they were 32 bytes apart -- every LDS-DMA piece one contiguous KiB)
-  const uint32_t rowbytes = (kClDbg & 32) ? 32u : (uint32_t)g.C * 2u;
+  const uint32_t rowbytes = (uint32_t)g.C * 2u;
 
   const uint32_t smem_off = lds_offset_of(smem);
   const uint32_t wid_u = (uint32_t)__builtin_amdgcn_readfirstlane(tid0 >> 6);
@@ -244,18 +192,16 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
   };
   const uint32_t soff[3] = {smem_off, smem_off + (uint32_t)STAGE, smem_off + 2u * (uint32_t)STAGE};
   // piece q of the stage at the pointer -> slot
-  bool dma_on = true;
   auto dma_piece = [&](int q, uint32_t slot_off) __attribute__((always_inline)) {
-    if ((kClDbg & 8) && !dma_on) return;
-    if (q < 2) buf_lds16(rs_xr, voa_c[q] + d_aoff, 0u, slot_off + (uint32_t)(q * 8192) + wave_lds);
-    else if (q < 4) buf_lds16(rs_xi, voa_c[q - 2] + d_aoff, 0u, slot_off + (uint32_t)(A_PLANE + (q - 2) * 8192) + wave_lds);
+    if (q < 2) buf_lds16_soff(rs_xr, voa_c[q] + d_aoff, 0u, slot_off + (uint32_t)(q * 8192) + wave_lds);
+    else if (q < 4) buf_lds16_soff(rs_xi, voa_c[q - 2] + d_aoff, 0u, slot_off + (uint32_t)(A_PLANE + (q - 2) * 8192) + wave_lds);
     else {
       const int j = q - 4;
       constexpr int FULLW = G::W_BYTES / 1024;             // waves of weight data in total
       const bool real = (uint32_t)(j * 8) + wid_u < (uint32_t)FULLW;
       const uint32_t dst = real ? slot_off + (uint32_t)(2 * A_PLANE + j * 8192) + wave_lds
                                 : smem_off + (uint32_t)G::DUMP + (wave_lds & 4095u);
-      buf_lds16(rs_w, vow[j], d_woff, dst);
+      buf_lds16_soff(rs_w, vow[j], d_woff, dst);
     }
   };
 
@@ -382,15 +328,6 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
   // ---- epilogue: 8 rows x 128 bytes per round through this wave's 2 KiB; NST unpredicated stores per wave (rows a
   // tile does not own -- the overlap with the next tile, rows past the tensor -- go to the dump buffer)
   auto epilogue = [&](int nt_) __attribute__((always_inline)) {
-    if (kClDbg & 4) {
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(acc_r[i][j]), "v"(acc_i[i][j]));
-#endif
-      return;
-    }
     const int t = opaque_tid();
     const int ln = t & 63, w_ = t >> 6, q31 = ln & 31, qk = ln >> 5;
     const int wm_ = w_ * 64;
@@ -428,11 +365,10 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
 #pragma unroll
           for (int sub = 0; sub < 2; ++sub) {
             const uint4 val = *reinterpret_cast<const uint4*>(reg + (sub * 8 + (ln >> 3)) * PITCH + (ln & 7) * 16);
-            if (kClDbg & 1) continue;
             const int m = wm_ + i * 32 + half * 16 + sub * 8 + (ln >> 3);
             const int col = nt_ * BN + (ln & 7) * 8;
             int64_t orow = (int64_t)r0 + m;
-            bool ok = m < own && !(kClDbg & 2);
+            bool ok = m < own;
             if (!out_dense) {                       // output image smaller than the grid: its own dense row index
               uint32_t w = w_first + (uint32_t)(i * 32 + half * 16 + sub * 8), h = h_first, b = b_first;
               if (wide) {                           // (W >= 64: one carry at most for the 64 rows of a wave)
@@ -445,12 +381,9 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
               orow = ((int64_t)b * g.Ho + h) * g.Wo + w;
             }
             bf16_t* dst = ok ? out + orow * ldc + col : reinterpret_cast<bf16_t*>(g.dump) + (int64_t)m * ldc + col;
-#ifndef CPLXAMD_CL_NO_NT          // streaming stores: the output is read by a later kernel, not by this one (-1.4 %)
+            // streaming stores: the output is read by a later kernel, not by this one (-1.4 %)
             typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
             __builtin_nontemporal_store(u32x4_t{val.x, val.y, val.z, val.w}, reinterpret_cast<u32x4_t*>(dst));
-#else
-            *reinterpret_cast<uint4*>(dst) = val;
-#endif
           }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
@@ -496,7 +429,7 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
 
   // start stagger: tiles take the same time on every CU, so without it all 256 CUs reach their epilogues together
   // and the 128 KiB per CU of stores arrive at the L2s / HBM as one burst per tile
-  if (!(kClDbg & 16)) {
+  {
     const int n = __builtin_amdgcn_readfirstlane(((int)blockIdx.x - g.stagger_from) * g.stagger);
     for (int i = 0; i < n; i += 32 * 64) __builtin_amdgcn_s_sleep(32);
   }
@@ -511,7 +444,6 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
   }
   wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
-  dma_on = false;
   init_acc();
   tile_masks();
   first_frags();
@@ -606,14 +538,6 @@ __global__ __launch_bounds__(256) void cl_to_nchw_kernel(const bf16_t* __restric
   }
 }
 
-static FastDiv make_div(uint32_t d) {
-  if (d <= 1) return FastDiv{0u, -1};
-  int s = 0;
-  while ((1ull << s) < d) ++s;                            // s = ceil(log2 d) >= 1
-  const uint64_t m = (((1ull << s) - d) << 32) / d + 1;   // ceil(2^(32+s) / d) - 2^32
-  return FastDiv{(uint32_t)m, s - 1};
-}
-
 }  // namespace cl
 }  // namespace cplxamd
 
@@ -694,8 +618,7 @@ int cplxamd_conv2d_cl_fl(const void* x_r, const void* x_i, const void* w_packed,
   g.tm_out = cl::TM - (KW - 1) * dil_w;
   g.tiles_m = (int)((P + g.tm_out - 1) / g.tm_out);
   g.tiles_n = N / 64;
-  g.div_w = cl::make_div((uint32_t)W); g.div_h = cl::make_div((uint32_t)H);
-  static const int stagger_pct = [] { const char* e = getenv("CPLXAMD_CL_STAGGER"); return e ? atoi(e) : 100; }();
+  g.div_w = make_div((uint32_t)W); g.div_h = make_div((uint32_t)H);
   const int ncu = device_cus() & ~7;
   const int64_t ntiles = (int64_t)g.tiles_m * g.tiles_n;
   if (ntiles > 0x7fffffff) return CPLXAMD_ESHAPE;
@@ -707,7 +630,7 @@ int cplxamd_conv2d_cl_fl(const void* x_r, const void* x_i, const void* w_packed,
   if (ntiles > 2 * grid && ntiles % grid) {
     const int64_t tile_clk = (int64_t)g.NS * 2 * 48 * 32 * 2;
     g.stagger_from = (int)(ntiles % grid);
-    g.stagger = (int)(tile_clk * stagger_pct / 100 / (grid - g.stagger_from));
+    g.stagger = (int)(tile_clk / (grid - g.stagger_from));
   }
   using G3 = cl::Geo<3>;
   static PerDeviceOnce attr_set;

@@ -22,14 +22,11 @@
 #include <type_traits>
 
 #include "common.h"
+#include "prims.h"
 #include "launch.h"   // per-call launch policy (CPLXAMD_LAUNCH_SHARED: the chip is shared with collectives)
 
 namespace cplxamd {
 namespace cl2 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NT = 512, TH = 16, TW = 32, BN = 64;
 constexpr int PH = TH + 2, PW = TW + 2, PPIX = PH * PW;       // 18 x 34 = 612 patch pixels, 32 B each per plane
@@ -65,33 +62,6 @@ struct Args {
   const float* scale_a; const float* scale_b; // device {s, 1 / s} of the two operands (nullptr: no scaling)
 #endif
 };
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ bf16x8 neg_frag(bf16x8 v) {
-  uint4 u = __builtin_bit_cast(uint4, v);
-  u.x ^= 0x80008000u; u.y ^= 0x80008000u; u.z ^= 0x80008000u; u.w ^= 0x80008000u;
-  return __builtin_bit_cast(bf16x8, u);
-}
-
-__device__ __forceinline__ void buf_lds16(i32x4 rsrc, uint32_t voff, uint32_t soff_uniform, uint32_t lds_off_uniform) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-               :
-               : "v"(voff), "s"(rsrc), "s"(lds_off_uniform), "s"(soff_uniform)
-               : "memory");
-#endif
-}
-
-__device__ __forceinline__ i32x4 make_rsrc(const void* base, uint32_t bytes) {
-  const uint64_t a = (uint64_t)(uintptr_t)base;
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
-  const uint32_t nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)bytes);
-  return i32x4{(int)lo, (int)(hi & 0xffffu), (int)nb, 0x00020000};
-}
 
 enum { FL_NORMAL = 0, FL_FIRST0 = 1, FL_LAST = 2, FL_FIRST1 = 3 };
 
@@ -204,8 +174,8 @@ __global__ __launch_bounds__(NT) void conv_cl2_kernel(Args g) {
 #endif
     const uint32_t voff = (nx ? voa_n[q] : voa_c[q]) + (uint32_t)cc * 32u;
     const uint32_t dst = smem_off + (uint32_t)(aslot * A_SLOT + q * 8192) + wave_lds;
-    if ((uint32_t)(q * 8) + wid_u < 20u) buf_lds16(rs_xr, voff, 0u, dst);
-    else buf_lds16(rs_xi, voff, 0u, dst);
+    if ((uint32_t)(q * 8) + wid_u < 20u) buf_lds16_soff(rs_xr, voff, 0u, dst);
+    else buf_lds16_soff(rs_xi, voff, 0u, dst);
   };
   // weights of (slice cs [of the next tile when past C / 16], kernel row kh) -> weight slot; the packed buffer is
   // ordered [column tile][kernel row][slice] (cplxamd_conv2d_cl_pack)
@@ -215,7 +185,7 @@ __global__ __launch_bounds__(NT) void conv_cl2_kernel(Args g) {
     const bool real = (uint32_t)(j * 8) + wid_u < (uint32_t)(W_BYTES / 1024);
     const uint32_t dst = real ? smem_off + (uint32_t)(A_RING + wslot * W_BYTES + j * 8192) + wave_lds
                               : smem_off + (uint32_t)DUMP + (wave_lds & 4095u);
-    buf_lds16(rs_w, vow[j], woff, dst);
+    buf_lds16_soff(rs_w, vow[j], woff, dst);
   };
 
   // fragment idx of tap kw of sub-stage (patch slot as, kernel row kh) -> register set st
@@ -236,7 +206,7 @@ __global__ __launch_bounds__(NT) void conv_cl2_kernel(Args g) {
   // the other set; `issue` puts this tap's LDS-DMA pieces behind the groups
   auto mfma_sub = [&](int st, int ras, int rkh, int rkw, bool do_read, auto issue) __attribute__((always_inline)) {
     bf16x8 nai[2];
-#ifndef CPLXAMD_CL2_ORD1   // first products of all four blocks, then the second ones (8 groups, one fragment read each): -0.7 % against four blocks x four products
+    // first products of all four blocks, then the second ones (8 groups, one fragment read each): -0.7 % against four blocks x four products
 #pragma unroll
     for (int ph = 0; ph < 2; ++ph)
 #pragma unroll
@@ -258,27 +228,6 @@ __global__ __launch_bounds__(NT) void conv_cl2_kernel(Args g) {
           if (g8 & 1) issue(g8 >> 1);
           __builtin_amdgcn_sched_barrier(0);
         }
-    return;
-#endif
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        if (j == 0) nai[i] = neg_frag(ai[st][i]);
-        acc_r[i][j] = CPLXAMD_MFMA16(br[st][j], ar[st][i], acc_r[i][j]);
-        acc_i[i][j] = CPLXAMD_MFMA16(br[st][j], ai[st][i], acc_i[i][j]);
-        acc_r[i][j] = CPLXAMD_MFMA16(bi[st][j], nai[i], acc_r[i][j]);
-        acc_i[i][j] = CPLXAMD_MFMA16(bi[st][j], ar[st][i], acc_i[i][j]);
-        const int grp = i * 2 + j;
-        __builtin_amdgcn_sched_barrier(0);
-        if (do_read) {
-          read_one(st ^ 1, ras, rkh, rkw, 2 * grp);
-          read_one(st ^ 1, ras, rkh, rkw, 2 * grp + 1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        issue(grp);
-        __builtin_amdgcn_sched_barrier(0);
-      }
   };
   auto none = [&](int) __attribute__((always_inline)) {};
 

@@ -25,22 +25,14 @@
 //
 // 3-slot ring, one s_barrier per stage, counted vmcnt (5 LDS-DMA pieces per wave and stage, nothing else in the loop);
 // fp32 slabs [split][tile][40 blocks][plane][32][32] and a deterministic reduce into dW[Co][Ci][3][3].
-#include <stdlib.h>
-
 #include "common.h"
+#include "prims.h"
 #include "launch.h"   // per-call launch policy (CPLXAMD_LAUNCH_SHARED: the chip is shared with collectives)
+#include "conv_cl_wgrad_common.h"
 
-#ifndef CLW_NT
-#define CLW_NT 3       // FOLD: nontemporal G stores (bit 0) / raw tile loads (bit 1)
-#endif
 namespace cplxamd {
 namespace clw {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int KR = 32, NT = 512, TC = 64;
@@ -73,68 +65,6 @@ struct Args {
   const float* coef;                               // [Co][kBnBwdCoef] (bn_bwd_finalize)
   void* dy_r; void* dy_i;                          // [P][Co] bf16 out: G as the MFMAs see it (the data gradient reads it next)
 };
-
-__device__ __forceinline__ void buf_lds16(i32x4 rsrc, uint32_t voff, uint32_t lds_off_uniform) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const uint32_t m0v = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_off_uniform);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-               :
-               : "v"(voff), "s"(rsrc), "s"(m0v)
-               : "memory");
-#endif
-}
-
-// the same for data that is read once (FOLD: the raw g / z tiles): nontemporal, so that it does not push the x rows -- each
-// fetched by three kernel rows -- out of the L2
-__device__ __forceinline__ void buf_lds16_nt(i32x4 rsrc, uint32_t voff, uint32_t lds_off_uniform) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const uint32_t m0v = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_off_uniform);
-#if CLW_NT & 2
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen nt lds"
-#else
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-#endif
-               :
-               : "v"(voff), "s"(rsrc), "s"(m0v)
-               : "memory");
-#endif
-}
-
-__device__ __forceinline__ i32x4 make_rsrc(const void* base, uint32_t bytes) {
-  const uint64_t a = (uint64_t)(uintptr_t)base;
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
-  const uint32_t nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)bytes);
-  return i32x4{(int)lo, (int)(hi & 0xffffu), (int)nb, 0x00020000};
-}
-
-// [k][64 channels] image, 128-B rows; the 64-B half is swapped on every other PAIR of k rows so that the 4 k rows one
-// 16-lane group of a transposed read touches fall into distinct banks (same image as conv_nhwc_wgrad.hip)
-__device__ __forceinline__ int img_off(int k, int chunk) { return k * 128 + ((chunk ^ (((k >> 1) & 1) << 2)) << 4); }
-
-// byte offset (inside an image) of this lane's transposed read for channels rb..rb+15, first pixel row kb:
-// lane m of a 16-lane group addresses T[kb + (m >> 2)][rb + 4 (m & 3)] and receives T[kb .. kb+3][rb + m]
-__device__ __forceinline__ uint32_t frag_base(int rb, int kb, int m) {
-  const int r = rb + 4 * (m & 3), k = kb + (m >> 2);
-  return (uint32_t)(img_off(k, r >> 3) + (r & 7) * 2);
-}
-// 8 consecutive pixels starting at the base row (+16 ks): two 4 x 16 transposes, rows +0 and +4 (the swizzle only
-// looks at bit 1 of the row, so +4 and +16 are plain byte offsets)
-__device__ __forceinline__ bf16x8 frag_at(const char* img, uint32_t base, int ks) {
-  s16x4 v[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-    v[h] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4*)(img + base + (ks * 16 + 4 * h) * 128));
-  const s16x8 both = __builtin_shufflevector(v[0], v[1], 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, both);
-}
-
-__device__ __forceinline__ bf16x8 neg(bf16x8 v) {
-  uint4 u = __builtin_bit_cast(uint4, v);
-  u.x ^= 0x80008000u; u.y ^= 0x80008000u; u.z ^= 0x80008000u; u.w ^= 0x80008000u;
-  return __builtin_bit_cast(bf16x8, u);
-}
 
 // compact tile index -> (co tile, ci tile) when the rectangle (co tile < sk_co, ci tile < sk_ci) is left out
 __device__ __forceinline__ void tile_of(int v, int tiles_ci, int sk_co, int sk_ci, int& tco, int& tci) {
@@ -412,11 +342,7 @@ __global__ __launch_bounds__(NT) void conv_cl_wgrad_kernel(Args g) {
   auto tile_store = [&]() __attribute__((always_inline)) {
     const uint32_t vs = ((int)vflag[0] < p_lim && writer) ? vo[0] + p_goff : OOB;
 #if defined(__HIP_DEVICE_COMPILE__)
-#if CLW_NT & 1
     asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen nt" : : "v"(gtile), "v"(vs), "s"(rs_dy) : "memory");
-#else
-    asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen" : : "v"(gtile), "v"(vs), "s"(rs_dy) : "memory");
-#endif
 #endif
   };
 
@@ -450,7 +376,7 @@ __global__ __launch_bounds__(NT) void conv_cl_wgrad_kernel(Args g) {
     char* g_img = smem + next_cur_off;
     // ---- sub-step 0 (entry: gr[0], gi[0], xr[0], xi[0] hold block 0 of this stage)
     {
-      const bf16x8 ngr = neg(gr[0]);
+      const bf16x8 ngr = neg_frag(gr[0]);
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
         const int cur = n & 1;
@@ -490,7 +416,7 @@ __global__ __launch_bounds__(NT) void conv_cl_wgrad_kernel(Args g) {
     }
     // ---- sub-step 1 (xr[0], xi[0] hold its block 0)
     {
-      const bf16x8 ngr = neg(gr[1]);
+      const bf16x8 ngr = neg_frag(gr[1]);
 #pragma unroll
       for (int n = 0; n < 3; ++n) {
         const int cur = n & 1;
@@ -614,29 +540,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* ws, int 
   dw[i] = emul ? acc * emul[i] : acc;
 }
 
-// Stage order of a split: down the image columns, 32-pixel strip by strip (1, default), or along the image rows (0:
-// CPLXAMD_CLW_WALK=0, the order of rounds 2-5).  A stage stages three x rows (one per kernel row); walking DOWN, two of the
-// three were fetched by the stage before and are still in the XCD's L2 -- along a row they come back eight stages later,
-// behind everything the other 31 workgroups of the XCD fetched meanwhile.  cfg3: 4.33 -> 4.09 ms (FOLD: 5.12 -> 5.01).
-static int stage_walk() {
-  static const int w = [] { const char* e = getenv("CPLXAMD_CLW_WALK"); return e ? (atoi(e) != 0) : 1; }();
-  return w;
-}
-
-// shared: the chip is shared with RCCL collectives (CPLXAMD_LAUNCH_SHARED): twice as many, half as long splits,
-// so that the workgroups that find their CU taken do not make the launch take two rounds (the workspace is always sized
-// for this plan)
-static int plan(int64_t nstages, int tiles, int& per_split, bool shared) {
-  const int ncu = device_cus();
-  int64_t s = ncu / tiles;                            // one workgroup per CU (120 KiB of LDS each), one round
-  if (s < 1) s = 1;
-  if (shared) s *= 2;
-  const int64_t maxs = (nstages + 15) / 16;           // >= 16 stages per split
-  if (s > maxs) s = maxs;
-  per_split = (int)((nstages + s - 1) / s);
-  return (int)((nstages + per_split - 1) / per_split);
-}
-
 }  // namespace clw
 }  // namespace cplxamd
 
@@ -659,7 +562,7 @@ int64_t cplxamd_conv2d_cl_wgrad_ws_bytes(int64_t B, int H, int W, int Ci, int Co
   if (B <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0) return 0;
   const int tiles = ((Co + 63) / 64) * ((Ci + 63) / 64);
   int per_split = 0;
-  const int splits = clw::plan(B * H * ((W + clw::KR - 1) / clw::KR), tiles, per_split, true);
+  const int splits = clw_plan(B * H * ((W + clw::KR - 1) / clw::KR), tiles, per_split, true);
   return (int64_t)splits * tiles * clw::NBLK * 2048 * 4;
 }
 
@@ -723,11 +626,13 @@ static int launch_clw(const void* g_r, const void* g_i, const void* x_r, const v
   g.nstages = (int)(B * H * g.strips);
   g.tiles_ci = Ci / 64;
   g.sk_co = skip_co / 64; g.sk_ci = skip_ci / 64;
-  g.walk = clw::stage_walk();
+  // stages walk DOWN the image columns, strip by strip: two of a stage's three x rows were fetched by the stage before and
+  // are still in the XCD's L2 (cfg3: 4.33 -> 4.09 ms against walking along the rows; FOLD: 5.12 -> 5.01)
+  g.walk = 1;
   const int tiles = (Co / 64) * g.tiles_ci - g.sk_co * g.sk_ci;
-  // (fewer tiles, more splits each: never more slabs than the workspace of the full tile count holds -- plan() rounds the
+  // (fewer tiles, more splits each: never more slabs than the workspace of the full tile count holds -- clw_plan() rounds the
   //  split count down to whole workgroups per tile)
-  g.splits = clw::plan(g.nstages, tiles, g.per_split, !launch_owns_chip(flags));
+  g.splits = clw_plan(g.nstages, tiles, g.per_split, !launch_owns_chip(flags));
   if ((int64_t)g.splits * tiles * clw::NBLK * 2048 * 4 > ws_bytes) return CPLXAMD_EWS;
   constexpr int smem = 3 * clw::STAGE;
   static PerDeviceOnce attr_set;
@@ -771,8 +676,8 @@ int cplxamd_conv2d_cl_wgrad_bn_fl(const void* g_r, const void* g_i, const void* 
   g.nstages = (int)(B * H * g.strips);
   g.tiles_ci = Ci / 64;
   const int tiles = (Co / 64) * g.tiles_ci;
-  g.splits = clw::plan(g.nstages, tiles, g.per_split, !launch_owns_chip(flags));
-  g.walk = clw::stage_walk();
+  g.splits = clw_plan(g.nstages, tiles, g.per_split, !launch_owns_chip(flags));
+  g.walk = 1;
   constexpr int smem = clw::SMEM_FOLD;
   static PerDeviceOnce attr_set;
   if (const int e = set_max_dyn_lds(attr_set, clw::conv_cl_wgrad_kernel<true>, smem)) return e;

@@ -2,19 +2,13 @@
 // bf16 planes, float32 out, optionally times an elementwise multiplier in the slab reduce (the d log_sigma2 of the
 // local-reparameterization layers: cplxmodule/nn/relevance/real/base.py:116-163).  Same work split (nine taps on eight
 // waves at four and a half 32 x 32 blocks each), same borders by out-of-range LDS-DMA, one plane and one MFMA per block.
-#include <stdlib.h>
-
 #include "common.h"
+#include "prims.h"
 #include "launch.h"   // per-call launch policy (CPLXAMD_LAUNCH_SHARED: the chip is shared with collectives)
+#include "conv_cl_wgrad_common.h"
 
 namespace cplxamd {
 namespace clwr {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KR = 32, NT = 512, TC = 64;
 constexpr int G_BYTES = 2 * KR * 128;              // [plane][32 pixels][64 co]
@@ -37,52 +31,6 @@ struct Args {
   int nstages, per_split, splits, tiles_ci;
   int walk;                                          // stage order: 0 = along image rows, 1 = down image columns (conv_cl_wgrad.hip)
 };
-
-__device__ __forceinline__ void buf_lds16(i32x4 rsrc, uint32_t voff, uint32_t lds_off_uniform) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const uint32_t m0v = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_off_uniform);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-               :
-               : "v"(voff), "s"(rsrc), "s"(m0v)
-               : "memory");
-#endif
-}
-
-__device__ __forceinline__ i32x4 make_rsrc(const void* base, uint32_t bytes) {
-  const uint64_t a = (uint64_t)(uintptr_t)base;
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
-  const uint32_t nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)bytes);
-  return i32x4{(int)lo, (int)(hi & 0xffffu), (int)nb, 0x00020000};
-}
-
-// [k][64 channels] image, 128-B rows; the 64-B half is swapped on every other PAIR of k rows so that the 4 k rows one
-// 16-lane group of a transposed read touches fall into distinct banks (same image as conv_nhwc_wgrad.hip)
-__device__ __forceinline__ int img_off(int k, int chunk) { return k * 128 + ((chunk ^ (((k >> 1) & 1) << 2)) << 4); }
-
-// byte offset (inside an image) of this lane's transposed read for channels rb..rb+15, first pixel row kb:
-// lane m of a 16-lane group addresses T[kb + (m >> 2)][rb + 4 (m & 3)] and receives T[kb .. kb+3][rb + m]
-__device__ __forceinline__ uint32_t frag_base(int rb, int kb, int m) {
-  const int r = rb + 4 * (m & 3), k = kb + (m >> 2);
-  return (uint32_t)(img_off(k, r >> 3) + (r & 7) * 2);
-}
-// 8 consecutive pixels starting at the base row (+16 ks): two 4 x 16 transposes, rows +0 and +4 (the swizzle only
-// looks at bit 1 of the row, so +4 and +16 are plain byte offsets)
-__device__ __forceinline__ bf16x8 frag_at(const char* img, uint32_t base, int ks) {
-  s16x4 v[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-    v[h] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4*)(img + base + (ks * 16 + 4 * h) * 128));
-  const s16x8 both = __builtin_shufflevector(v[0], v[1], 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, both);
-}
-
-__device__ __forceinline__ bf16x8 neg(bf16x8 v) {
-  uint4 u = __builtin_bit_cast(uint4, v);
-  u.x ^= 0x80008000u; u.y ^= 0x80008000u; u.z ^= 0x80008000u; u.w ^= 0x80008000u;
-  return __builtin_bit_cast(bf16x8, u);
-}
 
 // grid: x = split, y = co tile * tiles_ci + ci tile
 __global__ __launch_bounds__(NT) void conv_clr_wgrad_kernel(Args g) {
@@ -335,20 +283,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* ws, int 
   dw[i] = emul ? acc * (emul_exp ? __expf(emul[i]) : emul[i]) : acc;
 }
 
-// shared: the chip is shared with RCCL collectives (CPLXAMD_LAUNCH_SHARED): twice as many, half as long splits,
-// so that the workgroups that find their CU taken do not make the launch take two rounds (the workspace is always sized
-// for this plan)
-static int plan(int64_t nstages, int tiles, int& per_split, bool shared) {
-  const int ncu = device_cus();
-  int64_t s = ncu / tiles;                            // one workgroup per CU (120 KiB of LDS each), one round
-  if (s < 1) s = 1;
-  if (shared) s *= 2;
-  const int64_t maxs = (nstages + 15) / 16;           // >= 16 stages per split
-  if (s > maxs) s = maxs;
-  per_split = (int)((nstages + s - 1) / s);
-  return (int)((nstages + per_split - 1) / per_split);
-}
-
 }  // namespace clwr
 }  // namespace cplxamd
 
@@ -371,7 +305,7 @@ int64_t cplxamd_conv2d_clr_wgrad_ws_bytes(int64_t B, int H, int W, int Ci, int C
   if (B <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0) return 0;
   const int tiles = ((Co + 63) / 64) * ((Ci + 63) / 64);
   int per_split = 0;
-  const int splits = clwr::plan(B * H * ((W + clwr::KR - 1) / clwr::KR), tiles, per_split, true);
+  const int splits = clw_plan(B * H * ((W + clwr::KR - 1) / clwr::KR), tiles, per_split, true);
   return (int64_t)splits * tiles * clwr::NBLK * 1024 * 4;
 }
 
@@ -407,11 +341,8 @@ int cplxamd_conv2d_clr_wgrad_fl(const void* g_, const void* x, const float* emul
   g.nstages = (int)(B * H * g.strips);
   g.tiles_ci = Ci / 64;
   const int tiles = (Co / 64) * g.tiles_ci;
-  g.splits = clwr::plan(g.nstages, tiles, g.per_split, !launch_owns_chip(flags));
-  {
-    static const int w = [] { const char* e = getenv("CPLXAMD_CLW_WALK"); return e ? (atoi(e) != 0) : 1; }();
-    g.walk = w;
-  }
+  g.splits = clw_plan(g.nstages, tiles, g.per_split, !launch_owns_chip(flags));
+  g.walk = 1;
   constexpr int smem = 3 * clwr::STAGE;
   static PerDeviceOnce attr_set;
   if (const int e = set_max_dyn_lds(attr_set, clwr::conv_clr_wgrad_kernel, smem)) return e;

@@ -3,11 +3,9 @@
 // accumulators into contiguous NCHW runs through LDS.
 #pragma once
 #include "common.h"
+#include "prims.h"
 
 namespace cplxamd {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace cn {
 
 constexpr int BM = 256, BN = 64, NT = BM;
@@ -25,7 +23,7 @@ struct Args {
   int oh, ow;                   // grid position of output pixel (0, 0)
   int srows;                    // staged input rows per tile: BM + (KW-1)*dil_w
   int npieces;                  // LDS-DMA pieces per stage that carry data (the rest go to a dump slot)
-  int dbg;                      // ablation bit (CPLXAMD_CONV_DBG): 4 no stores
+  int dbg;                      // ablation bit 4: no stores (always 0: the launchers no longer set it)
 };
 
 struct __attribute__((packed, aligned(2))) bf8_t { uint4 v; };    // 16 B at 2-byte alignment

@@ -33,40 +33,22 @@
 // workgroups per CU (latency covered by occupancy instead of the 2-stage ring) does not exist for the
 // complex kernel: 128 accumulators + 126 other registers = 254 per lane, i.e. 2 waves per SIMD at most
 // (forcing 128 registers spills 750+).
-// Ablation of the final kernel (-DCONV_ABL=1 / 2 / 3, CPLXAMD_CONV_DBG=4; same box, cfg3 B=64 forward,
-// profiles/r01_conv_ablation.md): full 1.675 ms; without the epilogue stores 1.357; without LDS-DMA after
-// the prologue 1.397; without weight re-loads 1.506; with neither (MFMA + ds_read + barriers) 1.227, and
-// 0.856 ms when the stores are dropped too -- the MFMA floor is 0.59 ms at the power-limited clock.
-#include <stdlib.h>
-
+// Ablation of the final kernel (same box, cfg3 B=64 forward, profiles/r01_conv_ablation.md): full
+// 1.675 ms; without the epilogue stores 1.357; without LDS-DMA after the prologue 1.397; without weight
+// re-loads 1.506; with neither (MFMA + ds_read + barriers) 1.227, and 0.856 ms when the stores are
+// dropped too -- the MFMA floor is 0.59 ms at the power-limited clock.
 #include <type_traits>
 
 #include "conv_nhwc.h"
 
 namespace cplxamd {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace cn {
 
 constexpr int BK = 32;
-#ifndef CONV_ABL
-#define CONV_ABL 0      // ablation builds: bit 1 no LDS-DMA after the prologue, bit 2 no weight re-loads
-#endif
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
-  lds_dma16(gsrc, lds_wave_base);     // common.h: inline asm, invisible to the compiler's waitcnt pass
-}
 
 // 8 consecutive k of LDS row `row` (16-B chunk kc of 4); chunk slots XOR-swizzled per row group
 __device__ __forceinline__ bf16x8 frag(const char* plane, int row, int kc) {
   return *reinterpret_cast<const bf16x8*>(plane + row * 64 + ((kc ^ ((row >> 2) & 3)) << 4));
-}
-
-__device__ __forceinline__ bf16x8 neg(bf16x8 v) {
-  uint4 u = __builtin_bit_cast(uint4, v);
-  u.x ^= 0x80008000u; u.y ^= 0x80008000u; u.z ^= 0x80008000u; u.w ^= 0x80008000u;
-  return __builtin_bit_cast(bf16x8, u);
 }
 
 
@@ -160,7 +142,7 @@ __global__ __launch_bounds__(NT, 2) void conv_nhwc_kernel(Args g) {
         ar[ks][i] = frag(sA, r0 + i * 32, ks * 2 + lk);
         if (CPLX) ai[ks][i] = frag(sAi, r0 + i * 32, ks * 2 + lk);
       }
-    if (STAGE && !(CONV_ABL & 1)) {
+    if (STAGE) {
       // the whole next stage goes out NOW, ahead of this tap's weight re-loads: vmcnt counts in order,
       // so the first weight fragment consumed in the next tap forces everything older to have landed --
       // issued here the pieces get a full tap, interleaved further down they got half of one
@@ -175,7 +157,7 @@ __global__ __launch_bounds__(NT, 2) void conv_nhwc_kernel(Args g) {
       if (CPLX) {
         // y = x w: re -= xi wi, im += xr wi ;  y = x conj(w): re += xi wi, im -= xr wi
 #pragma unroll
-        for (int i = 0; i < 2; ++i) na[i] = neg(CONJ ? ar[ks][i] : ai[ks][i]);
+        for (int i = 0; i < 2; ++i) na[i] = neg_frag(CONJ ? ar[ks][i] : ai[ks][i]);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -195,7 +177,7 @@ __global__ __launch_bounds__(NT, 2) void conv_nhwc_kernel(Args g) {
           }
         }
       __builtin_amdgcn_sched_barrier(0);
-      if (!(CONV_ABL & 2)) load_b(tn, kwn, ks, br[ks], bi[ks]);           // this sub-step's set, for the next tap
+      load_b(tn, kwn, ks, br[ks], bi[ks]);           // this sub-step's set, for the next tap
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -271,8 +253,7 @@ __global__ __launch_bounds__(256) void nhwc_pad_kernel(const bf16_t* __restrict_
 template <typename TOUT, bool CPLX>
 static int launch_conj(const Args& g0, bool conj, hipStream_t st) {
   Args g = g0;
-  static const int dbg = getenv("CPLXAMD_CONV_DBG") ? atoi(getenv("CPLXAMD_CONV_DBG")) : 0;
-  g.dbg = dbg;
+  g.dbg = 0;
   g.npieces = 0;   // (field of the float32 kernel; the bf16 stage is 5 pieces per plane, always)
   int smem = 2 * (CPLX ? 2 : 1) * 5 * NT * 16;
   const int out_img = (sizeof(TOUT) == 2 ? (CPLX ? 2 : 1) : 1) * BN * OUT_LD * (int)sizeof(TOUT);

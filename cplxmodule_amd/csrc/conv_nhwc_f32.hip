@@ -13,8 +13,6 @@
 // matrix pipe; the exact-f32 gather kernel (conv.hip) stays for strides, groups and odd channels.
 //
 // Reference semantics: cplx.convnd (cplxmodule/cplx.py:717-838) and its autograd backward.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "conv_nhwc.h"
@@ -234,8 +232,7 @@ __global__ __launch_bounds__(256) void nhwc_pad_f32_kernel(const float* __restri
 template <typename TOUT, bool CPLX>
 static int launch_f32(const Args& g0, bool conj, hipStream_t st) {
   Args g = g0;
-  static const int dbg = getenv("CPLXAMD_CONV_DBG") ? atoi(getenv("CPLXAMD_CONV_DBG")) : 0;
-  g.dbg = dbg;
+  g.dbg = 0;
   g.npieces = ((CPLX ? 2 : 1) * g.srows * 4 + NT - 1) / NT;
   int smem = (2 * g.npieces + 1) * NT * 16;
   const int out_img = BN * OUT_LD * (int)sizeof(TOUT) * (sizeof(TOUT) == 2 && CPLX ? 2 : 1);

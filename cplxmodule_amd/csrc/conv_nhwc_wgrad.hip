@@ -15,26 +15,16 @@
 // 32 + (KW-1)*dil_w matching rows of Xp; tap kw reads its X fragments at row offset kw*dil_w, so the
 // KW taps share every staged byte.  3-stage LDS-DMA ring, counted vmcnt.  Partial tiles go to fp32
 // slabs [split][kh][kw][plane][64][64]; a small kernel sums them into dW[Cout][Cin][KH][KW].
-#include <stdlib.h>
-
 #include "common.h"
+#include "prims.h"
 
 namespace cplxamd {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace cw {
 
 constexpr int KR = 32;            // rows (GEMM k) per stage
 constexpr int TC = 64;            // channels per tile side
 constexpr int STAGES = 3;
 constexpr int MAXP = 8;           // LDS-DMA pieces per thread per stage at most
-#ifndef CW_ABL
-#define CW_ABL 0                  // ablation builds (bf16 kernel): bit 1 no LDS-DMA after the prologue, 2 no MFMA
-#endif
 
 struct Args {
   const bf16_t* g_r; const bf16_t* g_i;     // Gp [rows][Co]
@@ -47,16 +37,6 @@ struct Args {
   int npieces;
   int dbg;
 };
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
-  lds_dma16(gsrc, lds_wave_base);     // common.h: inline asm, invisible to the compiler's waitcnt pass
-}
-
-// [k][64 channels] image, 128-B rows; the 64-B half is swapped on every other PAIR of k rows so
-// that the 4 k rows one 16-lane group touches fall into distinct banks.
-__device__ __forceinline__ int img_off(int k, int chunk) {           // chunk: 16-B index 0..7
-  return k * 128 + ((chunk ^ (((k >> 1) & 1) << 2)) << 4);
-}
 
 // 8 consecutive k (starting at kb) of channel block rb..rb+15 as an MFMA fragment:
 // two hardware-transposed 4 x 16 reads (lane m of a 16-lane group: see gemm_bf16_impl.h)
@@ -71,12 +51,6 @@ __device__ __forceinline__ bf16x8 frag_t(const char* img, int rb, int kb, int m)
   }
   const s16x8 both = __builtin_shufflevector(v[0], v[1], 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(bf16x8, both);
-}
-
-__device__ __forceinline__ bf16x8 neg(bf16x8 v) {
-  uint4 u = __builtin_bit_cast(uint4, v);
-  u.x ^= 0x80008000u; u.y ^= 0x80008000u; u.z ^= 0x80008000u; u.w ^= 0x80008000u;
-  return __builtin_bit_cast(bf16x8, u);
 }
 
 __device__ __forceinline__ void wait_vmcnt_rt(int n) {   // wave-uniform n
@@ -195,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_nhwc_kernel(Args g) {
       bf16x8 nar[2];
       if (CPLX) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) nar[i] = neg(ar[ks][i]);
+        for (int i = 0; i < 2; ++i) nar[i] = neg_frag(ar[ks][i]);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -203,16 +177,15 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_nhwc_kernel(Args g) {
         for (int j = 0; j < 2; ++j) {
           // X fragment first: the accumulator holds the tile transposed, row (co) = lane & 31,
           // 4 consecutive ci per register group.  G conj(X): re = gr xr + gi xi, im = gi xr - gr xi
-          if (!(CW_ABL & 2))
           acc_r[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(br[ks][j], ar[ks][i], acc_r[i][j], 0, 0, 0);
-          if (CPLX && !(CW_ABL & 2)) {
+          if (CPLX) {
             acc_i[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(br[ks][j], ai[ks][i], acc_i[i][j], 0, 0, 0);
             acc_r[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bi[ks][j], ai[ks][i], acc_r[i][j], 0, 0, 0);
             acc_i[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bi[ks][j], nar[i], acc_i[i][j], 0, 0, 0);
           }
           if (q < MAXP) {
             __builtin_amdgcn_sched_barrier(0);
-            if (!(CW_ABL & 1)) stage_q(nbuf, tnext, q);
+            stage_q(nbuf, tnext, q);
             __builtin_amdgcn_sched_barrier(0);
             ++q;
           }
@@ -225,8 +198,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_nhwc_kernel(Args g) {
     stage_all(1, 1);
     int cur = 0;
     for (int t = 0; t < nt; ++t) {
-      if (CW_ABL & 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MAXP) : "memory");   // tile t landed; tile t+1 may be in flight
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MAXP) : "memory");   // tile t landed; tile t+1 may be in flight
       __builtin_amdgcn_s_barrier();
       int nxt = cur + 2; nxt = nxt >= STAGES ? nxt - STAGES : nxt;
       compute(cur, nxt, t + 2);
@@ -505,7 +477,7 @@ int cplxamd_conv2d_nhwc_wgrad(const void* gp_r, const void* gp_i, const void* xp
   cw::Args g{(const bf16_t*)gp_r, (const bf16_t*)gp_i, (const bf16_t*)xp_r, (const bf16_t*)xp_i,
              (float*)ws, rows, Wp, Co, Ci, KH, KW, dil_h, dil_w};
   g.splits = cw::plan_splits(rows, KH, tco * tci);
-  g.dbg = getenv("CPLXAMD_CONV_DBG") ? atoi(getenv("CPLXAMD_CONV_DBG")) : 0;
+  g.dbg = 0;
   const int64_t t_all = (rows + cw::KR - 1) / cw::KR;
   g.tiles_per_split = (int)((t_all + g.splits - 1) / g.splits);
   g.xrows = cw::KR + (KW - 1) * dil_w;

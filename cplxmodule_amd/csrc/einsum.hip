@@ -32,11 +32,10 @@
 #include <limits.h>
 
 #include "common.h"
+#include "prims.h"
 
 namespace cplxamd {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 enum { ELOAD_KFAST = 0, ELOAD_KVEC = 1, ELOAD_ROWS = 2, ELOAD_ROWVEC = 3 };
 constexpr int EG_B = CPLXAMD_EINSUM_BATCH, EG_M = CPLXAMD_EINSUM_M, EG_N = CPLXAMD_EINSUM_N, EG_K = CPLXAMD_EINSUM_K;

@@ -34,21 +34,15 @@
 //  * few output tiles + long K (wgrad at batch 2^20): split-K into fp32 slabs + a reduce kernel.
 // The experiment variants of rounds 2-3 (compile-time ablation bits, the classic per-tile pipeline, alternative MFMA
 // orders) were working COPIES of this header; they are in the history only (git show 1a9fb01:scripts/gemm_experiments/),
-// their results in profiles/r02_gemm_ablation.md / r03_gemm_pair_issue.txt.  Round 4's family (gemm_bf16_w4.hip) keeps
-// its ablation switches in the production file behind W4_BURST / W4_LDP / ... (scripts/r04/w4_build.sh; the W4_DBG / W4_PGRID / W4_PDYN ablations and the CPLXAMD_W4P_CPLX
-// selector left the file in round 6: scripts/r06/ablation_switches.patch puts them back).
-#include <stdlib.h>
-
+// their results in profiles/r02_gemm_ablation.md / r03_gemm_pair_issue.txt.  The compile-time switches of round 4's family
+// (gemm_bf16_w4.hip) are history too: the file holds the measured winners only (profiles/r04_gemm_w4_ab.txt,
+// r05_gemm_w4_persistent.txt; the losing branches: scripts/r04, scripts/r06/ablation_switches.patch and the git history).
 #include <type_traits>
 
 #include "gemm.h"
+#include "prims.h"
 
 namespace cplxamd {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 32, STAGES = 3;
 // complex: 256 x 128 tile, 4 x 2 waves of 64 x 64 (2 x 2 MFMA tiles x {re, im} = 128 accumulators);
@@ -122,19 +116,9 @@ __device__ __forceinline__ bf16x8 frag_t(const char* lds_plane, int rb, int kb, 
   return __builtin_bit_cast(bf16x8, both);
 }
 
-__device__ __forceinline__ bf16x8 neg_frag(bf16x8 v) {
-  uint4 u = __builtin_bit_cast(uint4, v);
-  u.x ^= 0x80008000u; u.y ^= 0x80008000u; u.z ^= 0x80008000u; u.w ^= 0x80008000u;
-  return __builtin_bit_cast(bf16x8, u);
-}
-
 // 16-byte epilogue stores (plain: nontemporal stores measured no gain for outputs a later kernel reads)
 __device__ __forceinline__ void nt_store16(void* p, uint4 v) { *reinterpret_cast<uint4*>(p) = v; }
 __device__ __forceinline__ void nt_store16(float* p, const f4& a) { st4(p, a); }
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <typename TOUT, bool CPLX, bool CONJ, bool TA, bool TB>
 __global__ __launch_bounds__((Cfg<CPLX>::NT), 2) void gemm_bf16_kernel(GemmArgs g) {
@@ -722,22 +706,9 @@ __global__ __launch_bounds__((Cfg<CPLX>::NT), 2) void gemm_bf16_kernel(GemmArgs 
   wait_vmcnt<0>();   // the branch-free K loop leaves (unused) LDS-DMA pieces in flight: land them before the LDS is released
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
 template <typename TOUT, bool CPLX, bool CONJ, bool TA, bool TB>
-static int launch_kernel_r(const GemmArgs& g0, hipStream_t st) {
+static int launch_kernel_r(const GemmArgs& g, hipStream_t st) {
   using C = Cfg<CPLX>;
-  // read-only tuning knobs, set once from the environment (A/B experiments only)
-  static const int order = env_int("CPLXAMD_GEMM_ORDER", 1), gm = env_int("CPLXAMD_GEMM_GROUP_M", 4);
-  GemmArgs g = g0;
-  static const int ldsepi = env_int("CPLXAMD_GEMM_LDSEPI", 1);   // A/B switch of the LDS-staged epilogue
-  g.lds_epilogue = ldsepi;
-  g.order = order; g.group_m = gm > 0 ? gm : 1;
   const int64_t tiles = (int64_t)((g.M + C::BM - 1) / C::BM) * ((g.N + C::BN - 1) / C::BN);
   if (tiles * g.splits > 0x7fffffff) return CPLXAMD_ESHAPE;
   if (g.plan) { *g.plan = 1; return 0; }
@@ -754,12 +725,10 @@ namespace cplxamd {
 
 // persistent form (gemm_bf16_persist.h): more than one round of full tiles, plain (bias-only) epilogue
 template <typename TOUT, bool CPLX, bool CONJ, bool TA, bool TB>
-static int launch_persist(const GemmArgs& g0, hipStream_t st, bool& taken) {
+static int launch_persist(const GemmArgs& g, hipStream_t st, bool& taken) {
   using C = Cfg<CPLX>;
   taken = false;
-  static const int enabled = env_int("CPLXAMD_GEMM_PERSIST", 1);     // (A/B at run time)
-  const GemmArgs& g = g0;
-  if (!enabled || !launch_owns_chip(g.flags)) return 0;
+  if (!launch_owns_chip(g.flags)) return 0;
   const int ncu = (g.ncu > 0 ? g.ncu : device_cus()) & ~7;
   if (g.splits > 1 || g.g1 || g.emul || g.accumulate || g.scale_a || (g.M % C::BM) || (g.N % C::BN) || g.K / BK < 12) return 0;
   if (g.fga && (!((CPLX ? CONJ : true) && TB && !TA && sizeof(TOUT) == 2) || (g.fld & 7) || !aligned16(g.fga) ||
@@ -777,9 +746,6 @@ static int launch_persist(const GemmArgs& g0, hipStream_t st, bool& taken) {
   if ((g.ldc & align) || !aligned16(g.c_r) || (CPLX && !aligned16(g.c_i))) return 0;
   if (g.bias_r && (!aligned16(g.bias_r) || (CPLX && !aligned16(g.bias_i)))) return 0;
   constexpr int smem = 3 * C::STAGE_BYTES + 16384;
-  GemmArgs a = g;
-  static const int gm = env_int("CPLXAMD_GEMM_GROUP_M", 4);
-  a.group_m = gm > 0 ? gm : 1;
   if constexpr (kInstantiated) {
     constexpr bool kFusable = (CPLX ? CONJ : true) && TB && kBf16Out;   // the LRT input gradient, complex and real (gemm.h: fga)
     auto go = [&](auto RR) -> int {
@@ -789,14 +755,14 @@ static int launch_persist(const GemmArgs& g0, hipStream_t st, bool& taken) {
         if (g.fga) {
           static PerDeviceOnce attr_set_f;
           if (const int e = set_max_dyn_lds(attr_set_f, gemm_bf16_persist_kernel<TOUT, CPLX, CONJ, TA, TB, R, true>, smem)) return e;
-          gemm_bf16_persist_kernel<TOUT, CPLX, CONJ, TA, TB, R, true><<<dim3((unsigned)ncu), C::NT, smem, st>>>(a);
+          gemm_bf16_persist_kernel<TOUT, CPLX, CONJ, TA, TB, R, true><<<dim3((unsigned)ncu), C::NT, smem, st>>>(g);
           CPLXAMD_CHECK_LAUNCH();
           return 0;
         }
       }
       static PerDeviceOnce attr_set;
       if (const int e = set_max_dyn_lds(attr_set, gemm_bf16_persist_kernel<TOUT, CPLX, CONJ, TA, TB, R>, smem)) return e;
-      gemm_bf16_persist_kernel<TOUT, CPLX, CONJ, TA, TB, R><<<dim3((unsigned)ncu), C::NT, smem, st>>>(a);
+      gemm_bf16_persist_kernel<TOUT, CPLX, CONJ, TA, TB, R><<<dim3((unsigned)ncu), C::NT, smem, st>>>(g);
       CPLXAMD_CHECK_LAUNCH();
       return 0;
     };
@@ -825,8 +791,7 @@ static int launch_kernel(const GemmArgs& g, hipStream_t st) {
   if (g.fga) {
     // the one-tile kernel carries the fused term in its LDS-staged bf16 epilogue only: the launch must be one that takes
     // that path with whole 16-byte column groups (same predicate as in the kernel), else decline -- never drop it silently
-    static const int ldsepi = env_int("CPLXAMD_GEMM_LDSEPI", 1);
-    const bool ok = sizeof(TOUT) == 2 && Cfg<CPLX>::JB == 2 && ldsepi && !g.g1 && !g.emul && !g.accumulate && g.splits <= 1 &&
+    const bool ok = sizeof(TOUT) == 2 && Cfg<CPLX>::JB == 2 && g.lds_epilogue && !g.g1 && !g.emul && !g.accumulate && g.splits <= 1 &&
                     !g.bias_r && (g.ldc & 7) == 0 && (g.fld & 7) == 0 && (g.N & 7) == 0 && aligned16(g.c_r) &&
                     (!CPLX || aligned16(g.c_i)) && aligned16(g.fga) && aligned16(g.fx_r) && (!CPLX || aligned16(g.fx_i));
     if (!ok) return CPLXAMD_ESHAPE;

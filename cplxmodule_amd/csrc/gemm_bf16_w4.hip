@@ -31,31 +31,15 @@
 //          tiles (u+3, u+4) as they drain
 // Preconditions (the launcher declines otherwise and the 8-wave kernels run): full tiles, K % 64 == 0, K >= 128, no
 // split-K, no Gauss combine, 16-byte aligned operands / outputs.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "gemm.h"
+#include "prims.h"
 
 namespace cplxamd {
 namespace w4 {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// where the two loads of a register pair go, in MFMA slots behind the pair's LDS write (experiments: scripts/r04/w4_build.sh)
-#ifndef W4_LDP
-#define W4_LDP 0
-#endif
-#ifndef W4_WAIT1
-#define W4_WAIT1 0   // 1: ONE s_waitcnt lgkmcnt(1) at the head of every K sub-step covers all fragment reads of the previous one
-#endif
-#ifndef W4_LDQ
-#define W4_LDQ 0
-#endif
 
 constexpr int BK = 32;
 
@@ -132,11 +116,6 @@ __device__ __forceinline__ uint32_t lane_t(int worg, int lane, int blk) {
   return (uint32_t)(k * (ROWS * 2) + (((r >> 3) ^ ((k & 3) << 2)) << 4) + (r & 7) * 2);
 }
 __device__ __forceinline__ uint32_t opaque(uint32_t x) { asm volatile("" : "+v"(x)); return x; }
-__device__ __forceinline__ bf16x8 neg_frag(bf16x8 v) {
-  uint4 u = __builtin_bit_cast(uint4, v);
-  u.x ^= 0x80008000u; u.y ^= 0x80008000u; u.z ^= 0x80008000u; u.w ^= 0x80008000u;
-  return __builtin_bit_cast(bf16x8, u);
-}
 __device__ __forceinline__ void store16(void* p, uint4 v) {
   *reinterpret_cast<uint4*>(p) = v;
 }
@@ -149,38 +128,16 @@ __device__ __forceinline__ void store16(float* p, const f4& a) {
 #define W4_VMCNT(N) __builtin_amdgcn_s_waitcnt(0x0F70 | ((N) & 0xF) | ((((N) >> 4) & 3) << 14))
 
 // ---- where the LDS writes sit among the MFMA slots of a K sub-step ---------------------------------------------------
-// spread (W4_BURST 0): every sub-step writes half of ITS tile parity's registers (NL / 2 writes): tile u+2 is written over
-//   the whole of tile u; the pair (P_j, Q_j) is re-requested behind Q_j's write, so P has 2 sub-steps (~2048 cycles) from
-//   request to use, Q has 4.
-// burst (W4_BURST 1): both registers of a pair are written in the one window in which both of their ring slots are free --
-//   second sub-step of the even tile, first of the odd one -- and re-requested at once: 4 sub-steps (~4096 cycles) for every
-//   load, at the price of NL writes + NL loads in each of those two sub-steps and none in the other two.
-#ifndef W4_BURST
-#define W4_BURST 0
-#endif
-constexpr int write_slot(bool cplx, bool burst, int k) {
-  if (!burst) return cplx ? 6 + 4 * k : (k == 0 ? 6 : k == 1 ? 9 : k == 2 ? 11 : 14);
-  if (cplx) { constexpr int t[12] = {6, 7, 10, 11, 12, 13, 14, 15, 18, 19, 20, 21}; return t[k]; }
-  constexpr int t[8] = {5, 6, 7, 9, 10, 11, 13, 14};
-  return t[k];
-}
-constexpr int slot_of_write(bool cplx, bool burst, int nw, int m, int off) {
+// Every sub-step writes half of ITS tile parity's registers (NL / 2 writes): tile u+2 is written over the whole of tile
+// u; the pair (P_j, Q_j) is re-requested right behind Q_j's write, so P has 2 sub-steps (~2048 cycles) from request to use,
+// Q has 4 (the measured alternatives: profiles/r04_gemm_w4_ab.txt).
+constexpr int write_slot(bool cplx, int k) { return cplx ? 6 + 4 * k : (k == 0 ? 6 : k == 1 ? 9 : k == 2 ? 11 : 14); }
+constexpr int slot_of_write(bool cplx, int nw, int m) {
   for (int k = 0; k < nw; ++k)
-    if (write_slot(cplx, burst, k) + off == m) return k;
+    if (write_slot(cplx, k) == m) return k;
   return -1;
 }
-// LDS operations a sub-step issues behind its last fragment read (the counted wait in front of the barrier)
-constexpr int ops_after_last_read(bool cplx, bool burst, bool writes) { return !writes ? 0 : !burst ? 1 : cplx ? 0 : 2; }
 
-#ifndef W4_EPI_PIPE
-#define W4_EPI_PIPE 1   // epilogue operands of round r + 1 requested ahead of the stores of round r (0: behind them, A/B)
-#endif
-#ifndef W4P_SPLIT
-#define W4P_SPLIT 0   // PERSIST: 1 = a select-free copy of the six-tile body for the steady part of the K range (see the K loop)
-#endif
-#ifndef W4P_RELOAD
-#define W4P_RELOAD 1   // PERSIST: re-request the next tile's K tiles 2, 3 behind the epilogue (see the tile loop)
-#endif
 // PERSIST (round 5 experiment, family bit 7; bf16 output, plain epilogue, no bias, (N,N) / (N,T)): ONE workgroup per CU walks
 // the tiles lin0, lin0 + grid, ... and the K-tile ring runs THROUGH the output-tile boundaries -- the loads the one-tile
 // form issues past the end of its K range (surplus, unused) fetch the NEXT tile's K tiles 0 .. 3 instead, so that tile's K
@@ -412,7 +369,7 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
   //   2 JB, 2 JB + 1     next A row 3 (other set)          [real: JB]
   //   (i+1) G, (i+1) G+1 next A row i = 0, 1, 2 (in place, behind the row's last MFMA)
   //   the NL / 2 LDS writes (odd tiles: each followed by the register pair's two loads) on the free slots in between
-  auto sub = [&](auto F, auto PAR, auto H, auto RS, auto RKS, auto WS, auto WS_P, auto WS_Q, int kt_next) __attribute__((always_inline)) {
+  auto sub = [&](auto F, auto PAR, auto H, auto RS, auto RKS, auto WS, int kt_next) __attribute__((always_inline)) {
     constexpr int f = decltype(F)::value, par = decltype(PAR)::value, h = decltype(H)::value;
     using I_F = std::integral_constant<int, f>;
     using I_G = std::integral_constant<int, 1 - f>;
@@ -437,33 +394,16 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
       if constexpr (m >= G && m % G == 0 && m / G <= IB - 1) rd_a(I_G{}, std::integral_constant<int, m / G - 1>{}, RS, RKS);
       if constexpr (CPLX && m >= G && m % G == 1 && m / G <= IB - 1) rd_ai(I_G{}, std::integral_constant<int, m / G - 1>{}, RS, RKS);
       // --- LDS writes + the loads that refill the registers (see write_slot above)
-      if constexpr (!W4_BURST) {
-        constexpr int wi = slot_of_write(CPLX, false, NW, m, 0), lp = slot_of_write(CPLX, false, NW, m, W4_LDP),
-                      lq = slot_of_write(CPLX, false, NW, m, W4_LDQ);
-        if constexpr (wi >= 0) write_piece(I_P{}, std::integral_constant<int, h * NW + (wi >= 0 ? wi : 0)>{}, WS);
+      constexpr int wi = slot_of_write(CPLX, NW, m);
+      if constexpr (wi >= 0) {
+        using PIECE = std::integral_constant<int, h * NW + wi>;
+        write_piece(I_P{}, PIECE{}, WS);
         if constexpr (par == 1) {
-          if constexpr (lp >= 0) { W4_SB(); load_piece(I0_{}, std::integral_constant<int, h * NW + (lp >= 0 ? lp : 0)>{}, kt_next); }
-          if constexpr (lq >= 0) { W4_SB(); load_piece(I1_{}, std::integral_constant<int, h * NW + (lq >= 0 ? lq : 0)>{}, kt_next); }
-        }
-      } else if constexpr (par != h) {
-        // window sub-step: (even tile, second half) writes pairs 0 .. NW-1, (odd tile, first half) pairs NW .. NL-1;
-        // k-th write: pair k / 2, register k % 2 (P -> slot of tile u+2, Q -> slot of tile u+3 = the even tile's own slot)
-        constexpr int k = slot_of_write(CPLX, true, NL, m, 0);
-        if constexpr (k >= 0) {
-          constexpr int q = (par == 0 ? 0 : NW) + (k >= 0 ? k : 0) / 2, reg = (k >= 0 ? k : 0) % 2;
-          if constexpr (reg == 0) write_piece(I0_{}, std::integral_constant<int, q>{}, WS_P);
-          else write_piece(I1_{}, std::integral_constant<int, q>{}, WS_Q);
-          if constexpr (reg == 1) {
-            W4_SB();
-            load_piece(I0_{}, std::integral_constant<int, q>{}, kt_next);
-            load_piece(I1_{}, std::integral_constant<int, q>{}, kt_next);
-          }
+          W4_SB(); load_piece(I0_{}, PIECE{}, kt_next);
+          W4_SB(); load_piece(I1_{}, PIECE{}, kt_next);
         }
       }
     };
-    // every fragment read of the previous sub-step is older than its last LDS write: one counted wait instead of one in
-    // front of each fragment's first use (the builtin is visible to the compiler's own wait insertion)
-    if constexpr (W4_WAIT1 != 0) __builtin_amdgcn_s_waitcnt(0xC07F | (ops_after_last_read(CPLX, W4_BURST, !W4_BURST || par == h) << 8));
     auto run = [&](auto self, auto MM) __attribute__((always_inline)) {
       constexpr int m = decltype(MM)::value;
       if constexpr (m < NM) {
@@ -542,21 +482,18 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
     using CUR = std::integral_constant<int, s>; using NXT = std::integral_constant<int, (s + 1) % 3>;
     using WR = std::integral_constant<int, (s + 2) % 3>;
     // the register pairs are re-requested with the K tiles two pairs ahead; past the end: the last pair again (unused)
-    constexpr int ahead = (W4_BURST && par == 0) ? 4 : 3;
+    constexpr int ahead = 3;
     int ktn = (t + ahead < nt) ? t + ahead : nt - 2;
     if constexpr (PERSIST) {
       ktn = t + ahead;                       // past the end of this tile's K range: the next tile's K tiles 0 .. 3
       if constexpr (par == 1) set_request(ktn, REDIR);
     }
-    // burst: P (tile u+2) -> even tile's WR slot = odd tile's NXT slot; Q (tile u+3) -> even tile's CUR = odd tile's WR
-    using WSP = std::conditional_t<par == 0, WR, NXT>;
-    using WSQ = std::conditional_t<par == 0, CUR, WR>;
-    sub(I0{}, PP, I0{}, CUR{}, I1{}, WR{}, WSP{}, WSQ{}, ktn);
-    // every wave: its F1 reads are complete (in-order LDS: all but the operations issued behind the last read)
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(ops_after_last_read(CPLX, W4_BURST, !W4_BURST || par == 1)) : "memory");
+    sub(I0{}, PP, I0{}, CUR{}, I1{}, WR{}, ktn);
+    // every wave: its F1 reads are complete (in-order LDS: all but the one LDS write issued behind the last read)
+    asm volatile("s_waitcnt lgkmcnt(1)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     W4_SB();
-    sub(I1{}, PP, I1{}, NXT{}, I0{}, WR{}, WSP{}, WSQ{}, ktn);
+    sub(I1{}, PP, I1{}, NXT{}, I0{}, WR{}, ktn);
   };
   // role swap of the per-slot LDS base registers: new[S] = old[(S + R) % 3]
   auto rotate = [&](auto R) __attribute__((always_inline)) {
@@ -575,20 +512,6 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
   {
     int t = 0;
     using RD = std::true_type;            // (only PERSIST looks at it)
-    if constexpr (PERSIST && W4P_SPLIT) {
-      // steady part: every request of the six tiles (K tiles t + 3 .. t + 8) lies inside this tile's K range.  (Measured
-      // as a compile: with two copies of the six-tile body the register allocator reconciles their accumulator
-      // assignments with 192 v_accvgpr moves INSIDE the first one -- off by default.)
-      for (; t + 9 <= nt; t += 6) {
-        using NR = std::false_type;
-        tile(I0{}, I0{}, t, NR{});
-        tile(I1{}, I1{}, t + 1, NR{});
-        tile(I2{}, I0{}, t + 2, NR{});
-        tile(I0{}, I1{}, t + 3, NR{});
-        tile(I1{}, I0{}, t + 4, NR{});
-        tile(I2{}, I1{}, t + 5, NR{});
-      }
-    }
     for (; t + 6 <= nt; t += 6) {
       tile(I0{}, I0{}, t, RD{});
       tile(I1{}, I1{}, t + 1, RD{});
@@ -706,7 +629,6 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
       for (int r = 0; r < NR; ++r) {
         const int pl = r / ((JB / 2) * (IB / 2)), jh = (r / (IB / 2)) % (JB / 2), ih = r % (IB / 2);
         const __amdgpu_buffer_rsrc_t rout = pl ? rout1 : rout0;
-        if constexpr (fuse && !W4_EPI_PIPE) { if (r > 0) load_ops(r); }
         // (PERSIST, complex: the compiler copies all 256 accumulators out of the AGPRs at the K loop's exit and spills ~56
         //  registers of the next tile's ring state around this epilogue.  Pinning the tuples in the AGPRs per round with an
         //  empty asm ("+a" on the 16-register tuple, or an asm v_accvgpr_read per element) makes the allocator shuffle
@@ -733,7 +655,7 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
               if constexpr (PERSIST) W4_SB();
             }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's tile is in LDS (in-order LDS, own region)
-        if constexpr (fuse && W4_EPI_PIPE) {
+        if constexpr (fuse) {
           if (r + 1 < NR) { W4_SB(); load_ops(r + 1); W4_SB(); }
         }
 #pragma unroll
@@ -777,7 +699,7 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
       // Rounds r = (plane, column half jh, block row i).  The multiplier / accumulate operands of round r + 1 are
       // requested BEFORE the stores of round r go out: vmcnt retires in issue order, so operands requested behind a
       // round's stores could not be used before every one of those stores was acknowledged -- one store-acknowledgement
-      // latency per round, eight per tile, in an epilogue nothing overlaps (W4_EPI_PIPE 0: that order, for the A/B).
+      // latency per round, eight per tile, in an epilogue nothing overlaps.
       constexpr int NR = NPL * (JB / 2) * IB;
       u32x4 mv[2][hm ? 8 : 1], pv[2][hacc ? 8 : 1];
       auto load_ops = [&](int r) __attribute__((always_inline)) {
@@ -794,7 +716,6 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
       for (int r = 0; r < NR; ++r) {
         const int pl = r / ((JB / 2) * IB), jh = (r / IB) % (JB / 2), i = r % IB;
         const __amdgpu_buffer_rsrc_t rout = pl ? rout1 : rout0;
-        if constexpr ((hm || hacc) && !W4_EPI_PIPE) { if (r > 0) load_ops(r); }
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
@@ -807,7 +728,7 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
             st4(reinterpret_cast<float*>(reg + l31 * PITCH + cl * 4), v);
           }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr ((hm || hacc) && W4_EPI_PIPE) {
+        if constexpr (hm || hacc) {
           if (r + 1 < NR) { W4_SB(); load_ops(r + 1); W4_SB(); }
         }
 #pragma unroll
@@ -861,7 +782,7 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
     // the fragments of the new tile's first K sub-step once more (the last K sub-step read them already: re-reading
     // here makes those 48 registers free during the epilogue -- an LDS round trip per tile against spilled ring state)
     first_frags();
-    if constexpr (W4P_RELOAD && CPLX) {      // (the real kernel has the registers: nothing is spilled there)
+    if constexpr (CPLX) {      // (the real kernel has the registers: nothing is spilled there)
       // the new tile's K tiles 2, 3 ONCE MORE: the look-ahead requested them before the epilogue, but registers that stay
       // live across it are what the allocator spills around it (complex: 96 staging registers beside 256 accumulators on
       // their way out).  Re-requested here, the earlier request is a prefetch into the L2 and the registers are free.
@@ -870,7 +791,7 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
     }
     // nothing of the boundary (the stores, reloads of whatever the allocator spilled around the epilogue) may be in flight
     // when the K loop's counted waits start counting: they are the same static instructions in every trip
-    if constexpr (!(W4P_RELOAD && CPLX)) W4_VMCNT(0);
+    if constexpr (!CPLX) W4_VMCNT(0);
   }
   } while (true);
 }
@@ -888,18 +809,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_w4p_kernel(GemmArgs g) {
   w4_tile<bf16_t, CPLX, CONJ, false, TB, true>(g, (int)blockIdx.x, smem);
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
 template <typename TOUT, bool CPLX, bool CONJ, bool TA, bool TB>
 static int launch(const GemmArgs& g0, hipStream_t st) {
   using C = Cfg<CPLX>;
   GemmArgs g = g0;
-  static const int gm = env_int("CPLXAMD_GEMM_GROUP_M", 4);
-  g.group_m = gm > 0 ? gm : 1;
   const int64_t tiles = (int64_t)(g.M / C::BM) * (g.N / C::BN);
   if constexpr (sizeof(TOUT) == 2 && !TA && !CPLX) {      // (complex: not instantiated, see below)
     // round 5 (family bit 7): the ring through the tile boundaries; needs the chip (one workgroup per CU), more than one
@@ -972,15 +885,15 @@ int launch_gemm_bf16_w4(const GemmArgs& g, bool cplx, int out_dtype, bool ta, bo
   const int64_t lda = ta ? g.a_cs : g.a_rs, ldb = tb ? g.b_cs : g.b_rs;
   if ((lda % 8) || (ldb % 8) || lda >= (1 << 22) || ldb >= (1 << 22)) return 0;      // 32-bit per-lane tile offsets
   if (g.ldc >= (1 << 20) || g.fld >= (1 << 20)) return 0;                             // ... of the epilogue (256 rows x 4 bytes)
-  if (!w4::aligned16(g.a_r) || !w4::aligned16(g.b_r) || !w4::aligned16(g.c_r)) return 0;
-  if (cplx && (!w4::aligned16(g.a_i) || !w4::aligned16(g.b_i) || !w4::aligned16(g.c_i))) return 0;
-  if (g.bias_r && (!w4::aligned16(g.bias_r) || (cplx && !w4::aligned16(g.bias_i)))) return 0;
+  if (!aligned16(g.a_r) || !aligned16(g.b_r) || !aligned16(g.c_r)) return 0;
+  if (cplx && (!aligned16(g.a_i) || !aligned16(g.b_i) || !aligned16(g.c_i))) return 0;
+  if (g.bias_r && (!aligned16(g.bias_r) || (cplx && !aligned16(g.bias_i)))) return 0;
   if (out_dtype == CPLXAMD_BF16) {
     if ((g.ldc & 7) || g.emul || g.accumulate) return 0;
-    if (g.fga && ((g.fld & 7) || !w4::aligned16(g.fga) || !w4::aligned16(g.fx_r) || (cplx && !w4::aligned16(g.fx_i)) || g.bias_r))
+    if (g.fga && ((g.fld & 7) || !aligned16(g.fga) || !aligned16(g.fx_r) || (cplx && !aligned16(g.fx_i)) || g.bias_r))
       return 0;
   } else if (out_dtype == CPLXAMD_F32) {
-    if ((g.ldc & 3) || g.fga || (g.emul && !w4::aligned16(g.emul))) return 0;
+    if ((g.ldc & 3) || g.fga || (g.emul && !aligned16(g.emul))) return 0;
     if (cplx && g.emul && !g.emul_both) return 0;      // (a multiplier on the real plane only: nothing launches that)
   } else {
     return 0;

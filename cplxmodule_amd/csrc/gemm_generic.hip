@@ -11,10 +11,10 @@
 // {re, im}), BK = 16, operands staged k-major in LDS (register-prefetched, double-buffered) so
 // that every ds_read_b32 is conflict-free; split-K for few-tile / long-K shapes.
 #include "gemm.h"
+#include "prims.h"
 
 namespace cplxamd {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int GBK = 16;
 // Tile = 64 NB x 64 NB outputs per 256-thread block (waves 2 x 2, each NB x NB MFMA tiles x {re, im}): NB = 2 for problems

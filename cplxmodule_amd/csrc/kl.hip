@@ -21,12 +21,7 @@ namespace cplxamd {
 
 constexpr int kKlThreads = 256;
 constexpr int kKlMaxBlocks = 2048;
-#ifndef KL_UNROLL
-#define KL_UNROLL 1     // (2 and 4 measured 2-4 % slower on the fused kernel: profiles/r06_kl_pmc.txt)
-#endif
-#ifndef KL_NT
-#define KL_NT 3       // bit 0: nontemporal gradient stores, bit 1: nontemporal operand loads (read once, written once: +3-8 % on the fused kernel, +10 % on the value kernel; profiles/r06_kl_pmc.txt)
-#endif
+constexpr int kKlUnroll = 1;   // (2 and 4 measured 2-4 % slower on the fused kernel: profiles/r06_kl_pmc.txt)
 
 constexpr float kEulerGamma = 0.57721566490153286f;
 constexpr float kK1 = 0.63576f, kK2 = 1.87320f, kK3 = 1.48695f;
@@ -263,22 +258,16 @@ struct KlArgs {
   bf16_t* s_b = nullptr;
 };
 
+// nontemporal gradient stores and operand loads (read once, written once: +3-8 % on the fused kernel, +10 % on the value
+// kernel; profiles/r06_kl_pmc.txt)
 __device__ __forceinline__ void st4g(float* p, const f4& v) {
-#if KL_NT & 1
   typedef float f4v __attribute__((ext_vector_type(4)));
   __builtin_nontemporal_store(f4v{v.v[0], v.v[1], v.v[2], v.v[3]}, reinterpret_cast<f4v*>(p));
-#else
-  st4(p, v);
-#endif
 }
 __device__ __forceinline__ f4 ld4g(const float* p) {
-#if KL_NT & 2
   typedef float f4v __attribute__((ext_vector_type(4)));
   const f4v t = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p));
   return f4{{t.x, t.y, t.z, t.w}};
-#else
-  return ld4(p);
-#endif
 }
 
 template <int KIND, bool VALUE, bool GRAD>
@@ -374,12 +363,12 @@ __global__ __launch_bounds__(kKlThreads) void kl_kernel(KlArgs a) {
       st4(a.s_b + 4 * i, e);
     }
   };
-  // KL_UNROLL vector indices per thread and iteration, every load issued before the first result is needed (the loop
+  // kKlUnroll vector indices per thread and iteration, every load issued before the first result is needed (the loop
   // is latency-bound otherwise: three dependent 16-byte loads per thread in flight against ~2 us of HBM latency)
-  for (int64_t i0 = (int64_t)blockIdx.x * kKlThreads + threadIdx.x; i0 < n4; i0 += KL_UNROLL * stride) {
-    f4 wr[KL_UNROLL], ls[KL_UNROLL], wi[KL_UNROLL], ge[KL_UNROLL];
+  for (int64_t i0 = (int64_t)blockIdx.x * kKlThreads + threadIdx.x; i0 < n4; i0 += kKlUnroll * stride) {
+    f4 wr[kKlUnroll], ls[kKlUnroll], wi[kKlUnroll], ge[kKlUnroll];
 #pragma unroll
-    for (int u = 0; u < KL_UNROLL; ++u) {
+    for (int u = 0; u < kKlUnroll; ++u) {
       const int64_t i = i0 + u * stride;
       wi[u] = f4{{0.f, 0.f, 0.f, 0.f}};
       ge[u] = f4{{1.f, 1.f, 1.f, 1.f}};
@@ -391,7 +380,7 @@ __global__ __launch_bounds__(kKlThreads) void kl_kernel(KlArgs a) {
       }
     }
 #pragma unroll
-    for (int u = 0; u < KL_UNROLL; ++u) {
+    for (int u = 0; u < kKlUnroll; ++u) {
       const int64_t i = i0 + u * stride;
       if (i < n4) body(i, wr[u], ls[u], wi[u], ge[u]);
     }

@@ -625,8 +625,8 @@ class _Pieces:
 
 
 # float32 split products: keep the input's bf16 pieces (6 bytes per element and plane, + 6 for |x|^2) from the forward for
-# the backward's weight gradients instead of splitting again (one HBM pass per plane less; CPLXAMD_X3_SAVE=0: remake them)
-_X3_SAVE = os.environ.get("CPLXAMD_X3_SAVE", "1") != "0"
+# the backward's weight gradients instead of splitting again (one HBM pass per plane less) whenever the forward's and the
+# backward's kinds agree; otherwise the backward splits again.
 
 
 def _cplx_linear_fwd(x2r, x2i, wr, wi, bias, algo=0, mode=None, xs=None):
@@ -662,17 +662,13 @@ def _cplx_linear_dx(g2r, g2i, wr, wi, out_dtype, algo=0, mode=None, gs=None):
                  algo=algo if gauss_ok(B, I, O) and I % 8 == 0 else 0)
 
 
-_LRT_DX_FUSE = os.environ.get("CPLXAMD_LRT_DX_FUSE", "1") != "0"     # (A/B switch; results are bit-identical)
-_EARLY_W = os.environ.get("CPLXAMD_DP_EARLY_W", "1") != "0"           # (A/B switch: announce dW before the variance dW)
-
-
 def _cplx_lrt_dx(g2r, g2i, wr, wi, x2r, x2i, ga, mode=None, gs=None):
     """Input gradient of the complex LRT layer: dX = G conj(W) + 2 X (*) ga in ONE launch when the persistent bf16
     kernel takes the shape (cplxamd_cgemm_lrt_dx: the elementwise term rides in its epilogue), otherwise the GEMM and
     the accumulate pass -- bit-identical results either way (tests/test_gpu_r03.py)."""
     B, O = g2r.shape
     I = wr.shape[1]
-    if (_LRT_DX_FUSE and _is_bf16(g2r) and _is_bf16(x2r) and _is_bf16(ga) and _is_bf16(wr) and I % 8 == 0 and O % 8 == 0
+    if (_is_bf16(g2r) and _is_bf16(x2r) and _is_bf16(ga) and _is_bf16(wr) and I % 8 == 0 and O % 8 == 0
             and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (g2r, g2i, wr, wi, x2r, x2i, ga))):
         dxr = torch.empty(B, I, dtype=torch.bfloat16, device=g2r.device)
         dxi = torch.empty_like(dxr)
@@ -689,7 +685,7 @@ def _real_lrt_dx(g2, w, x2, ga, mode=None, gs=None):
     bf16 kernel takes the shape, else the GEMM and the accumulate pass (bit-identical)."""
     B, O = g2.shape
     I = w.shape[1]
-    if (_LRT_DX_FUSE and _is_bf16(g2) and _is_bf16(x2) and _is_bf16(ga) and _is_bf16(w) and I % 8 == 0 and O % 8 == 0
+    if (_is_bf16(g2) and _is_bf16(x2) and _is_bf16(ga) and _is_bf16(w) and I % 8 == 0 and O % 8 == 0
             and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (g2, w, x2, ga))):
         dx = torch.empty(B, I, dtype=torch.bfloat16, device=g2.device)
         if try_call("cplxamd_rgemm_lrt_dx_fl", ptr(g2), O, 1, ptr(w), 1, I, ptr(x2), ptr(ga), I, ptr(dx), I, B, I, O,
@@ -858,7 +854,7 @@ class CplxLinearFn(torch.autograd.Function):
         xs = _Pieces(x2r, x2i)
         yr, yi, ctx.wc = _cplx_linear_fwd(x2r, x2i, wmr, wmi, bias, algo, mode=ctx.mode, xs=xs)
         ctx.kind = x3.take(O, I, x2r.shape[0], mode=ctx.mode) if xs.v is not None else None     # (the weight gradient's)
-        keep = xs.saved() if (_X3_SAVE and ctx.kind and xs.v[0].kind == ctx.kind) else (None, None, None)
+        keep = xs.saved() if (ctx.kind and xs.v[0].kind == ctx.kind) else (None, None, None)
         # (xr, xi as given: the create_graph backward needs graph-connected tensors, and x2r / x2i are views or copies made
         #  here, without history; for a contiguous input they share its storage)
         ctx.save_for_backward(x2r, x2i, wr, wi, mask, *keep, xr, xi)
@@ -975,7 +971,7 @@ class CplxLinearLRTFn(torch.autograd.Function):
             a = None                                         # |x|^2 exists as 16-bit pieces only
             s2 = x3.gemm_nn(xa.get(use3), (x3.split(ls2c, x3.SPLIT_B, op=x3.OP_EXP, kind=use3),), B, O, I)
             ctx.kind = x3.take(O, I, B, mode=mode)           # the weight gradients' arithmetic (K = batch)
-            if _X3_SAVE and ctx.kind == use3:                # they will read the same pieces
+            if ctx.kind == use3:                # they will read the same pieces
                 keep = (*xs.saved(), *xa.saved())
         else:
             mur, mui = cgemm(x2r, x2i, (I, 1), wcr, wci, (I, 1), B, O, I, bias=bias, out_dtype=x2r.dtype)
@@ -1060,8 +1056,7 @@ class CplxLinearLRTFn(torch.autograd.Function):
                     dwi.add_(klg[2] * gkl)
             # two thirds of the layer's gradient bytes are final here: their buckets' all-reduces may start under the
             # variance weight gradient already (0.25 ms earlier than behind the announcement below)
-            if _EARLY_W:
-                _announce(wr, wi)
+            _announce(wr, wi)
         if need[6]:
             if fused:
                 dls2 = klg[0]
@@ -1073,8 +1068,6 @@ class CplxLinearLRTFn(torch.autograd.Function):
                     dls2.add_(klg[0] * gkl)
         if fused or getattr(ctx, "klg_shared", False):
             ctx.klg = None                                   # consumed (or about to be overwritten by the hook's copy): the buffers hold totals now
-        if not _EARLY_W:
-            _announce(wr if dwr is not None else None, wi if dwi is not None else None)
         _announce(ls2 if dls2 is not None else None, br if dbr is not None else None, bi if dbi is not None else None)
         if need[0] or need[1]:
             if ctx.S is None:                                # gs2 . exp(ls2) -> [B,I], sigma^2 formed in the split pass
@@ -1105,7 +1098,7 @@ class RealLinearFn(torch.autograd.Function):
         y, wm = _real_linear_fwd(x2, wm, _c(b), mode=ctx.mode, xs=xs)
         ctx.wm = wm
         ctx.kind = x3.take(O, I, x2.shape[0], mode=ctx.mode) if xs.v is not None else None
-        keep = xs.saved() if (_X3_SAVE and ctx.kind and xs.v[0].kind == ctx.kind) else (None, None)
+        keep = xs.saved() if (ctx.kind and xs.v[0].kind == ctx.kind) else (None, None)
         ctx.save_for_backward(x2, w, mask, *keep, x)         # (x as given: see CplxLinearFn.forward)
         ctx.has_bias, ctx.lead = b is not None, x.shape[:-1]
         return y.view(*ctx.lead, O)
@@ -1197,7 +1190,7 @@ class RealLinearLRTFn(torch.autograd.Function):
             a = None
             s2 = x3.gemm_nn(xa.get(use3), (x3.split(ls2c, x3.SPLIT_B, op=x3.OP_EXP, kind=use3),), B, O, I)
             ctx.kind = x3.take(O, I, B, mode=mode)
-            if _X3_SAVE and ctx.kind == use3:
+            if ctx.kind == use3:
                 keep = (*xs.saved(), *xa.saved())
         else:
             mu = rgemm(x2, (I, 1), wb, (I, 1), B, O, I, bias=_c(b), out_dtype=x2.dtype)

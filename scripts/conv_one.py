@@ -1,4 +1,4 @@
-"""One bf16 complex conv forward shape, timed with HIP events (ablation runs: CPLXAMD_CONV_DBG)."""
+"""One bf16 complex conv forward shape, timed with HIP events."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -28,5 +28,5 @@ def timeit(fn, iters=10, warm=3):
 flop = 8.0 * B * Co * oshape[2] * oshape[3] * C * K * K
 t = timeit(lambda: conv.conv_fwd(xr, xi, wr, wi, None, None, geom, oshape))
 tp = timeit(lambda: conv.input_grid(xr, xi, geom))
-print(f"dbg={os.environ.get('CPLXAMD_CONV_DBG', '0')} fwd {t:.3f} ms (pad passes {tp:.3f} ms) -> kernel ~{t - tp:.3f} ms = "
+print(f"fwd {t:.3f} ms (pad passes {tp:.3f} ms) -> kernel ~{t - tp:.3f} ms = "
       f"{flop / (t - tp) / 1e9:.0f} TF/s")
