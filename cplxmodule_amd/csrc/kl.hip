@@ -130,6 +130,30 @@ template <int KIND> __device__ __forceinline__ constexpr float kl_ls2_term() {
   return KIND == CPLXAMD_KL_CPLX_VD_SCALEFREE ? -0.5f : 0.0f;
 }
 
+// One element's penalty: kl_value(t) + c * ls2.  Two extension kinds have values that cross zero while their terms do
+// not, where a float32 ulp of a TERM (and the float32 gamma, 3.3e-9 after the halving) is no small error of the sum:
+//   bogus      t = 2 log(|w| + 1e-12) - ls2 itself, near t = 0 with both terms small;
+//   scalefree  (f(t) - gamma) / 2 - ls2 / 2, near ls2 = f(t) - gamma.
+// Those few elements redo the cancelling sum in double (the others return the float32 expression unchanged).
+template <int KIND>
+__device__ __forceinline__ float kl_elem_value(float t, float ls, float wr, float wi) {
+  if (KIND == CPLXAMD_KL_CPLX_VD_BOGUS) {
+    // (only with |ls2| and |ln |w|^2| both small -- |w| ~ 1, ls2 ~ 0: elsewhere an ulp of either term is a relative error
+    // of that term, here the 1-ulp square root alone shifts t by 1.2e-7 absolutely)
+    if (fabsf(ls) + fabsf(t + ls) < 0.5f)
+      return (float)(2.0 * log(sqrt((double)wr * wr + (double)wi * wi) + 1e-12) - (double)ls);
+    return t;
+  }
+  if (KIND == CPLXAMD_KL_CPLX_VD_SCALEFREE) {
+    const float f = cplx_vd_value(t);
+    const float v = 0.5f * (f - kEulerGamma) + -0.5f * ls;
+    if (fabsf(v) < 0.03125f * (f + kEulerGamma + fabsf(ls)))
+      return (float)(0.5 * ((double)f - 0.57721566490153286) - 0.5 * (double)ls);
+    return v;
+  }
+  return kl_value<KIND>(t) + kl_ls2_term<KIND>() * ls;
+}
+
 // f'(t)
 template <int KIND>
 __device__ __forceinline__ float kl_slope(float t) {
@@ -299,6 +323,10 @@ __global__ __launch_bounds__(kKlThreads) void kl_kernel(KlArgs a) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const f2 x = f2{q[2 * h] * exp_neg(ls.v[2 * h]), q[2 * h + 1] * exp_neg(ls.v[2 * h + 1])};
+        // x past the float32 range (t > 88.7, or exp(-log_sigma2) overflowing on its own: inf or inf - inf): gamma + ln x
+        // is not finite there although the penalty gamma + t is; the formulas below work from t.  (Far from 104, where
+        // E1 left: up to 2^100 the value arm is gamma + ln x on a finite x.)
+        tiny |= !(x.x < 0x1p100f) | !(x.y < 0x1p100f);
         f2 v, sl;
         cplx_vd_pair(x, v, sl);
         if (VALUE) { val.v[2 * h] = v.x; val.v[2 * h + 1] = v.y; }
@@ -335,7 +363,7 @@ __global__ __launch_bounds__(kKlThreads) void kl_kernel(KlArgs a) {
         float theta;
         const float t = -log_alpha_of<CPLX, false>(ls.v[j], wr.v[j], wi.v[j], theta);
         if (VALUE) {
-          val.v[j] = kl_value<KIND>(t) + kLs * ls.v[j];
+          val.v[j] = kl_elem_value<KIND>(t, ls.v[j], wr.v[j], wi.v[j]);
           part += val.v[j];
         }
         if (GRAD) {
@@ -407,7 +435,7 @@ __global__ __launch_bounds__(kKlThreads) void kl_kernel(KlArgs a) {
       float theta;
       const float t = -log_alpha_of<CPLX, false>(ls, wr, wi, theta);
       if (VALUE) {
-        const float v = kl_value<KIND>(t) + kLs * ls;
+        const float v = kl_elem_value<KIND>(t, ls, wr, wi);
         acc += (double)v;
         if (a.out_elem) a.out_elem[i] = v;
       }

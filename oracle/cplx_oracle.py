@@ -548,6 +548,32 @@ def penalty(kind, log_sigma2, wr, wi=None):
     raise ValueError(kind)
 
 
+def penalty_exact(kind, log_sigma2, wr, wi=None):
+    """Float64 penalty without the cancellation of `penalty`'s literal gamma + t - Ei(-e^t): that expression is ~x
+    for small x = e^t and carries an error of ~eps64 |t| / x there (useless as a 2e-6 yardstick below x ~ 1e-9).
+      x <= 1: f = -sum_{k>=1} (-x)^k / (k k!)   (the series of E1 with gamma + ln x cancelled analytically)
+      x  > 1: f = gamma + t + E1(x)             (E1 underflowing to 0 at large x is correct)
+    with t = 2 ln(|w| + 1e-12) - log_sigma2 exactly as `log_alpha` forms it.  The two Ei kinds only; the other kinds
+    have no cancellation and delegate to `penalty`.  The slope is `penalty_dt` as before."""
+    if kind not in ("cplx_vd", "cplx_vd_scalefree"):
+        return penalty(kind, log_sigma2, wr, wi)
+    from scipy.special import exp1
+    ls2 = np.asarray(log_sigma2, np.float64)
+    t = -log_alpha(ls2, np.asarray(wr, np.float64), None if wi is None else np.asarray(wi, np.float64))
+    with np.errstate(over="ignore"):
+        x = np.exp(t)
+    xs = np.minimum(x, 1.0)
+    series, term = np.zeros_like(xs), np.ones_like(xs)
+    for k in range(1, 41):              # |term| <= 1 / k!: below 1e-47 at k = 40
+        term = term * (-xs) / k
+        series = series - term / k
+    with np.errstate(invalid="ignore"):
+        f = np.where(x <= 1.0, series, EULER_GAMMA + t + exp1(np.maximum(x, 1.0)))
+    if kind == "cplx_vd":
+        return f
+    return (f - EULER_GAMMA) / 2 - ls2 / 2   # log|w| - ls2 - Ei(-x)/2 = (f - gamma)/2 - ls2/2
+
+
 def penalty_dt(kind, t):
     """f'(t) with t = -log_alpha."""
     dt = t.dtype
