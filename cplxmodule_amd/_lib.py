@@ -186,6 +186,13 @@ SIGNATURES = {
     "cplxamd_init_moments": [_P, _P, _L, _I, _P, _P, _P],
     "cplxamd_init_ns_poly": [_P, _P, _P, _P, _I, _D, _D, _I, _P, _P, _P],
     "cplxamd_init_scale_store": [_P, _P, _P, _P, _L, _L, _I, _I, _D, _P, _P, _I, _I, _P],
+    # still ABI 25: structured compaction of the masked layers (compact.py)
+    "cplxamd_live_index_ws_bytes": [_L, _L],
+    "cplxamd_live_index": [_P, _L, _L, _L, _I, _P, _P, _P, _P, _P, _P, _L, _P],
+    "cplxamd_gather_axis": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
+    "cplxamd_expand_axis": [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
+    "cplxamd_compact_weight": [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _I, _I, _P],
+    "cplxamd_expand_weight": [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _I, _I, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -203,6 +210,7 @@ CPLX_FN = {"exp": 0, "log": 1, "sin": 2, "cos": 3, "tan": 4, "sinh": 5, "cosh": 
 _RESTYPES = {"cplxamd_absmax_ws_bytes": c_int64, "cplxamd_init_ws_bytes": c_int64, "cplxamd_conv2d_cl2_mom_chunks": c_int64, "cplxamd_conv2d_cl2_mom_chunks_fl": c_int64, "cplxamd_vd_kl_ws_bytes": c_int64, "cplxamd_lrt_reparam_bwd_cols_ws_bytes": c_int64, "cplxamd_l0_gate_bwd_ws_bytes": c_int64, "cplxamd_bn_ws_bytes": c_int64,
              "cplxamd_conv2d_wgrad_ws_bytes": c_int64, "cplxamd_conv2d_bf16_wgrad_ws_bytes": c_int64, "cplxamd_colsum_ws_bytes": c_int64, "cplxamd_gemm_ws_bytes": c_int64,
              "cplxamd_cgemm3m_ws_bytes": c_int64,
+             "cplxamd_live_index_ws_bytes": c_int64,
              "cplxamd_conv2d_nhwc_wgrad_ws_bytes": c_int64,
              "cplxamd_conv2d_nhwc_wgrad_f32_ws_bytes": c_int64,
              "cplxamd_conv2d_cl_pack_bytes": c_int64, "cplxamd_conv2d_cl_ws_bytes": c_int64,

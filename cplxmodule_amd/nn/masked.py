@@ -11,10 +11,17 @@ import torch
 from .modules.linear import CplxLinear, CplxBilinear
 from .modules.conv import CplxConv1d, CplxConv2d, CplxConv3d
 from .utils.sparsity import SparsityStats
-from .. import cplx, ops
+from .. import compact as _compact, cplx, ops
 
 
 class BaseMasked(torch.nn.Module):
+    # the opt-in route on compacted operands (cplxmodule_amd/compact.py, imported as `_compact`: the flag below has the
+    # module's name; `compact_`): plain attributes -- neither buffers
+    # nor state_dict entries, untouched by mask_() and load_state_dict
+    compact = False
+    compact_max_live = None          # None: compact.MAX_LIVE_FRACTION
+    _compact_kind = None             # "linear" / "conv2d" on the layers that have the route
+
     def __init__(self):
         super().__init__()
         self.register_buffer("mask", None)
@@ -27,6 +34,7 @@ class BaseMasked(torch.nn.Module):
         """Set (tensor) or drop (None) the sparsity mask."""
         if mask is not None and not isinstance(mask, torch.Tensor):
             raise TypeError(f"`mask` must be either a Tensor or `None`. Got {type(mask).__name__}.")
+        self.__dict__.pop("_compact_plan", None)      # (the cached index lists belong to the mask that goes away)
         if mask is None:
             if self.is_sparse:
                 del self.mask
@@ -93,7 +101,12 @@ class _MaskedStats(BaseMasked, SparsityStats):
 
 
 class CplxLinearMasked(CplxLinear, _MaskedStats):
+    _compact_kind = "linear"
+
     def forward(self, input):
+        plan = _compact.route(self, input.real)
+        if plan is not None:
+            return _compact.linear(self, input, plan)
         # the mask rides in the GEMM operand preparation / weight-gradient epilogue (ops.CplxLinearFn)
         w, b = self.weight, self.bias
         br, bi = (None, None) if b is None else (b.real, b.imag)
@@ -107,7 +120,12 @@ class CplxLinearMasked(CplxLinear, _MaskedStats):
 
 
 class CplxConv2dMasked(CplxConv2d, _MaskedStats):
+    _compact_kind = "conv2d"
+
     def forward(self, input):
+        plan = _compact.route(self, input.real)
+        if plan is not None:
+            return _compact.conv2d(self, input, plan)
         return cplx.conv2d(input, self.weight_masked, self.bias, self.stride, self.padding,
                            self.dilation, self.groups, self.padding_mode)
 
@@ -172,7 +190,12 @@ class Conv3dMasked(torch.nn.Conv3d, _RealMaskedStats):
 
 
 class LinearMasked(torch.nn.Linear, _MaskedStats):
+    _compact_kind = "linear"
+
     def forward(self, input):
+        plan = _compact.route(self, input)
+        if plan is not None:
+            return _compact.linear(self, input, plan)
         return ops.RealLinearFn.apply(input, self.weight, self.bias, self._require_mask())
 
     def sparsity(self, *, hard=True, **kwargs):
@@ -180,8 +203,13 @@ class LinearMasked(torch.nn.Linear, _MaskedStats):
 
 
 class Conv2dMasked(torch.nn.Conv2d, _MaskedStats):
+    _compact_kind = "conv2d"
+
     def forward(self, input):
         from .. import conv
+        plan = _compact.route(self, input)
+        if plan is not None:
+            return _compact.conv2d(self, input, plan)
         if self.padding_mode != "zeros":
             raise ValueError("Conv2dMasked supports `zeros` padding only")
         return conv.RealConv2dFn.apply(input, self.weight_masked, self.bias, self.stride,
@@ -199,6 +227,25 @@ def named_masks(module, prefix=""):
     for name, mod in module.named_modules(prefix=prefix):
         if isinstance(mod, BaseMasked):
             yield name, mod.mask
+
+
+def compact_(module, enabled=True, max_live=None):
+    """Switch the route on compacted operands on or off for every masked submodule that has one ({Cplx,}LinearMasked,
+    {Cplx,}Conv2dMasked; the other masked layers ignore the flag).  With the route on, a layer whose mask has dead rows
+    (output features) or dead columns (input features) runs the dense kernels on the live ones only, whenever the padded
+    product O' I' is strictly below O I and at most `max_live` O I (None: compact.MAX_LIVE_FRACTION).  Layers with
+    groups > 1, float64 layers and weights under a data-parallel hook stay dense.  Returns `module`."""
+    for mod in module.modules():
+        if isinstance(mod, BaseMasked) and mod._compact_kind is not None:
+            mod.compact = bool(enabled)
+            mod.compact_max_live = None if max_live is None else float(max_live)
+    return module
+
+
+def compaction(module):
+    """{name: None | dict(rows=(live, padded, total), cols=(live, padded, total), active=bool)} for every masked
+    submodule; None: the layer has no compact route, or no mask.  (Builds a stale plan: one host synchronisation.)"""
+    return {name: _compact.report(mod) for name, mod in module.named_modules() if isinstance(mod, BaseMasked)}
 
 
 def deploy_masks(module, *, state_dict=None, prefix="", reset=False):

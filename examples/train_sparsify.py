@@ -124,6 +124,8 @@ def main(argv=None):
     ap.add_argument("--threshold", type=float, default=1.0)
     ap.add_argument("--graph", action="store_true", help="capture each phase's training step in a hipGraph")
     ap.add_argument("--time", action="store_true", help="print the wall time of the three phases")
+    ap.add_argument("--compact", action="store_true",
+                    help="masked phase: run layers whose masks have dead rows / columns on compacted operands (masked.compact_)")
     a = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -151,6 +153,10 @@ def main(argv=None):
     fine = Net(masked.CplxLinearMasked, a.width).to(dev)
     fine.load_state_dict(state, strict=False)
     masked.deploy_masks(fine, state_dict=masks)
+    if a.compact:
+        masked.compact_(fine)
+        if rank == 0:
+            print("compaction:", masked.compaction(fine))
     h3 = train(fine, x, y, a.steps, 0.0, 1e-3, world > 1, a.graph)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0

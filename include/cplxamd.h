@@ -1040,6 +1040,44 @@ int cplxamd_init_scale_store(const void* in_r, const void* in_i, void* out_r, vo
                              int transpose, int mode, double target, const double* moments, double* status, int in_dtype,
                              int out_dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Structured compaction of the masked layers (cplxmodule_amd/compact.py; csrc/compact.hip).  New exports under ABI 25:
+ * nothing existing changes.  A masked layer whose mask has dead rows (output features) or dead columns (input features)
+ * runs the dense kernels on gathered operands and expands the results.  Every kernel is a deterministic copy (no
+ * atomics), capturable, on CPLXAMD_F32 or CPLXAMD_BF16 planes; a second plane (`*_i`) is optional and always comes with
+ * its output.  Index lists are int32.
+ *   cplxamd_live_index      mask float32 [O, C, T] (T = 1: a linear weight; a convolution weight has T = kh kw).  rows /
+ *                           cols: the ascending lists of the indices o / c with any(mask[o, :, :] != 0) /
+ *                           any(mask[:, c, :] != 0), padded with the LOWEST-numbered dead indices (list kept ascending) up
+ *                           to min(total, the next multiple of `granule`); an empty live set stays empty.  inv_rows[O] /
+ *                           inv_cols[C]: position in the list, or -1.  counts (device int32[4]) = live rows, listed rows,
+ *                           live columns, listed columns.  rows / cols must hold O / C entries (only the listed prefix
+ *                           is written).  1 <= O, C, T <= 2^20 (else CPLXAMD_ESHAPE); ws: cplxamd_live_index_ws_bytes(O, C).
+ *   cplxamd_gather_axis     out[o, j, i] = src[o, idx[j], i]: src [outer, axis, inner] -> out [outer, n_idx, inner].
+ *   cplxamd_expand_axis     its adjoint as ONE pass over the full output (no memset, no scatter):
+ *                           out[o, a, i] = inv[a] >= 0 ? src[o, inv[a], i] : fill[a]   (fill float32 [axis], NULL: 0),
+ *                           src [outer, n_idx, inner] -> out [outer, axis, inner].
+ *                           Both move 16 bytes per lane where inner and the pointers allow it, single elements otherwise.
+ *   cplxamd_compact_weight  out[r, c, t] = w[rows[r], cols[c], t] * mask[rows[r], cols[c], t], w [O, C, T] ->
+ *                           out [n_rows, n_cols, T] converted to out_dtype (the compacted cplxamd_mask_mul).
+ *   cplxamd_expand_weight   its adjoint: out[o, c, t] = src[inv_rows[o], inv_cols[c], t] * mask[o, c, t] where both
+ *                           inverse entries are >= 0, else an exact 0; src [n_rows, n_cols, T] -> out [O, C, T].
+ * ---------------------------------------------------------------------------------- */
+int64_t cplxamd_live_index_ws_bytes(int64_t O, int64_t C);
+int cplxamd_live_index(const float* mask, int64_t O, int64_t C, int64_t T, int granule, int* rows, int* cols, int* inv_rows,
+                       int* inv_cols, int* counts, void* ws, int64_t ws_bytes, void* stream);
+int cplxamd_gather_axis(const void* src_r, const void* src_i, const int* idx, void* out_r, void* out_i, int64_t outer,
+                        int64_t axis, int64_t n_idx, int64_t inner, int dtype, void* stream);
+int cplxamd_expand_axis(const void* src_r, const void* src_i, const int* inv, const float* fill_r, const float* fill_i,
+                        void* out_r, void* out_i, int64_t outer, int64_t n_idx, int64_t axis, int64_t inner, int dtype,
+                        void* stream);
+int cplxamd_compact_weight(const void* w_r, const void* w_i, const float* mask, const int* rows, const int* cols, void* out_r,
+                           void* out_i, int64_t O, int64_t C, int64_t T, int64_t n_rows, int64_t n_cols, int in_dtype,
+                           int out_dtype, void* stream);
+int cplxamd_expand_weight(const void* src_r, const void* src_i, const float* mask, const int* inv_rows, const int* inv_cols,
+                          void* out_r, void* out_i, int64_t O, int64_t C, int64_t T, int64_t n_rows, int64_t n_cols,
+                          int in_dtype, int out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
