@@ -126,6 +126,7 @@ SIGNATURES = {
     "cplxamd_conv2d_ktab_fill": [_P, _I, _P],
     "cplxamd_conv2d_bf16_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "cplxamd_conv2d_bf16_dgrad": [_P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "cplxamd_conv2d_bf16_dgrad_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P],      # (still ABI 25: an export added)
     "cplxamd_conv2d_bf16_wgrad_ws_bytes": [_P, _I],
     "cplxamd_conv2d_bf16_wgrad": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P],
     "cplxamd_chansum": [_P, _P, _L, _I, _L, _I, _P, _P],

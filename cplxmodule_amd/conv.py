@@ -494,9 +494,11 @@ def conv_fwd(xr, xi, wr, wi, br, bi, geom, out_shape, keep_grid=False):
     return done(None)
 
 
-def conv_dgrad(gr, gi, wr, wi, geom, x_shape, gp=None):
-    """gp: grad_grid(gr, gi, geom) if the caller already made it (shared with conv_wgrad)."""
-    dxr = torch.empty(x_shape, dtype=gr.dtype, device=gr.device)
+def conv_dgrad(gr, gi, wr, wi, geom, x_shape, gp=None, out_dtype=None):
+    """gp: grad_grid(gr, gi, geom) if the caller already made it (shared with conv_wgrad).
+    out_dtype: torch.float32 for the unrounded sums of bf16 operands (the transposed convolution adds its bias to them)."""
+    out_dtype = gr.dtype if out_dtype is None else out_dtype
+    dxr = torch.empty(x_shape, dtype=out_dtype, device=gr.device)
     dxi = None if gi is None else torch.empty_like(dxr)
     if geom[0] == 0:
         return dxr, dxi
@@ -521,6 +523,17 @@ def conv_dgrad(gr, gi, wr, wi, geom, x_shape, gp=None):
                     geom[11], geom[12], 1, -_shift_rows(geom), geom[9], geom[10], x_shape[2],
                     x_shape[3], dtype_code(dxr), stream_ptr()):
             return dxr, dxi
+    if out_dtype != gr.dtype:
+        # float32 sums of bf16 operands: the gather kernel stores them too; what it declines (stride, K % 32) goes to the
+        # float32 kernels on the (exactly) widened operands
+        if geom[7] == 1 and geom[8] == 1:
+            wtr = _repack_dgrad(wr, geom[13])
+            wti = None if wi is None else _repack_dgrad(wi, geom[13])
+            if try_call("cplxamd_conv2d_bf16_dgrad_f32", ptr(gr), ptr(gi), ptr(wtr), ptr(wti), ptr(dxr), ptr(dxi), geom,
+                        ptr(_ktab(geom, 1, gr.device)), stream_ptr()):
+                return dxr, dxi
+        wide = lambda t: None if t is None else ops.cast(t, out_dtype)  # noqa: E731
+        return conv_dgrad(wide(gr), wide(gi), wide(wr), wide(wi), geom, x_shape)
     if gr.dtype == torch.bfloat16 and geom[7] == 1 and geom[8] == 1:
         wtr = _repack_dgrad(wr, geom[13])
         wti = None if wi is None else _repack_dgrad(wi, geom[13])
@@ -1234,9 +1247,14 @@ class CplxConvTranspose2dFn(torch.autograd.Function):
         if tuple(oshape) != tuple(xr.shape):
             raise ValueError("output_padding must be smaller than either stride or dilation")
         vr, vi = ops.cast(wr.contiguous(), xr.dtype), ops.cast((-wi).contiguous(), xr.dtype)
-        yr, yi = conv_dgrad(xr, xi, vr, vi, geom, yshape)
-        if br is not None:
-            yr, yi = yr + br.view(1, -1, 1, 1).to(yr.dtype), yi + bi.view(1, -1, 1, 1).to(yi.dtype)
+        if br is not None and xr.dtype == torch.bfloat16:
+            # the bias joins the float32 sums BEFORE their one rounding to bf16 (added to the rounded result it rounds twice)
+            yr, yi = conv_dgrad(xr, xi, vr, vi, geom, yshape, out_dtype=torch.float32)
+            yr, yi = (yr + br.view(1, -1, 1, 1)).to(xr.dtype), (yi + bi.view(1, -1, 1, 1)).to(xr.dtype)
+        else:
+            yr, yi = conv_dgrad(xr, xi, vr, vi, geom, yshape)
+            if br is not None:
+                yr, yi = yr + br.view(1, -1, 1, 1).to(yr.dtype), yi + bi.view(1, -1, 1, 1).to(yi.dtype)
         ctx.save_for_backward(xr, xi, vr, vi)
         ctx.geom, ctx.has_bias, ctx.wshape, ctx.xshape = geom, br is not None, wr.shape, xr.shape
         return yr, yi

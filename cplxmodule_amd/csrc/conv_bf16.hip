@@ -42,6 +42,7 @@ struct ConvFArgs {
   int ktab_n;
   const float* bias_r; const float* bias_i;
   void* yr; void* yi;
+  int out_f32;                          // FWD / DGRAD: store the float32 sums instead of their bf16 rounding
   ConvFP p;
   int64_t M, N, K;
   int splits; int64_t kchunk;
@@ -301,7 +302,7 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(ConvFArgs a) {
       vr += a.bias_r[g * p.Cog + m];
       if (CPLX) vi += a.bias_i[g * p.Cog + m];
     }
-    if (MODE == FMODE_WGRAD || MODE == FMODE_WGRAD_ROWS) {
+    if (MODE == FMODE_WGRAD || MODE == FMODE_WGRAD_ROWS || a.out_f32) {
       reinterpret_cast<float*>(a.yr)[o] = vr;
       if (CPLX) reinterpret_cast<float*>(a.yi)[o] = vi;
     } else {
@@ -433,9 +434,8 @@ int cplxamd_conv2d_bf16_fwd(const void* xr, const void* xi, const void* wr, cons
 }
 
 /* wtr / wti: weight repacked to [groups][Ci/g][Co/g * KH * KW] (K-contiguous for the dgrad GEMM) */
-int cplxamd_conv2d_bf16_dgrad(const void* gr, const void* gi, const void* wtr, const void* wti,
-                              void* dxr, void* dxi, const int* geom, const int* ktab,
-                              void* stream) {
+static int bf16_dgrad(const void* gr, const void* gi, const void* wtr, const void* wti, void* dxr, void* dxi,
+                      const int* geom, const int* ktab, int out_f32, void* stream) {
   if (!gr || !wtr || !dxr || !geom || !ktab) return CPLXAMD_EINVAL;
   const bool cplx = gi != nullptr;
   if (cplx && (!wti || !dxi)) return CPLXAMD_EINVAL;
@@ -447,9 +447,21 @@ int cplxamd_conv2d_bf16_dgrad(const void* gr, const void* gi, const void* wtr, c
   a.K = (int64_t)p.Cog * p.KH * p.KW;
   if (a.K % FBK || !al16(wtr) || (cplx && !al16(wti))) return CPLXAMD_ESHAPE;
   a.ar = (const bf16_t*)wtr; a.ai = (const bf16_t*)wti; a.br = (const bf16_t*)gr; a.bi = (const bf16_t*)gi;
-  a.ktab = ktab; a.ktab_n = (int)a.K; a.yr = dxr; a.yi = dxi;
+  a.ktab = ktab; a.ktab_n = (int)a.K; a.yr = dxr; a.yi = dxi; a.out_f32 = out_f32;
   a.M = p.Cg; a.N = (int64_t)p.B * p.H * p.W; a.splits = 1; a.kchunk = a.K;
   return conv_bf16_launch<FMODE_DGRAD>(a, cplx, true, (hipStream_t)stream);
+}
+
+int cplxamd_conv2d_bf16_dgrad(const void* gr, const void* gi, const void* wtr, const void* wti,
+                              void* dxr, void* dxi, const int* geom, const int* ktab,
+                              void* stream) {
+  return bf16_dgrad(gr, gi, wtr, wti, dxr, dxi, geom, ktab, 0, stream);
+}
+
+int cplxamd_conv2d_bf16_dgrad_f32(const void* gr, const void* gi, const void* wtr, const void* wti,
+                                  float* dxr, float* dxi, const int* geom, const int* ktab,
+                                  void* stream) {
+  return bf16_dgrad(gr, gi, wtr, wti, dxr, dxi, geom, ktab, 1, stream);
 }
 
 int64_t cplxamd_conv2d_bf16_wgrad_ws_bytes(const int* geom, int cplx) {

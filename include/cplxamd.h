@@ -564,6 +564,11 @@ int cplxamd_conv2d_bf16_fwd(const void* xr, const void* xi, const void* wr, cons
 int cplxamd_conv2d_bf16_dgrad(const void* gr, const void* gi, const void* wtr, const void* wti,
                               void* dxr, void* dxi, const int* geom, const int* ktab,
                               void* stream);
+/* The same data gradient with the float32 sums stored unrounded (dxr / dxi float32): for a caller that still adds to them
+ * before the one rounding to bf16 (the transposed convolution's bias). */
+int cplxamd_conv2d_bf16_dgrad_f32(const void* gr, const void* gi, const void* wtr, const void* wti,
+                                  float* dxr, float* dxi, const int* geom, const int* ktab,
+                                  void* stream);
 int64_t cplxamd_conv2d_bf16_wgrad_ws_bytes(const int* geom, int cplx);
 int cplxamd_conv2d_bf16_wgrad(const void* gr, const void* gi, const void* xr, const void* xi,
                               const float* emul, float* dwr, float* dwi, const int* geom,
