@@ -189,15 +189,23 @@ def _cl_wgrad_ok(geom):
     return _CL_FORCE or 8.0 * P * Ci * Co * 9 >= _CL_MIN_FLOP
 
 
+def _cl_wgrad_args(geom, w_shape, device, real=False):
+    """What the weight-gradient entry points of csrc/conv_cl_wgrad.hip (complex, real, batch-norm fold) marshal alike:
+    -> (an empty float32 dW plane, the arguments they end in, from B through the slab workspace to the stream)."""
+    B, Ci, Co, H, W = (geom[i] for i in range(5))
+    ws_bytes = getattr(_lib.load(), "cplxamd_conv2d_clr_wgrad_ws_bytes" if real else "cplxamd_conv2d_cl_wgrad_ws_bytes")
+    ws = _scratch(device, int(ws_bytes(B, H, W, Ci, Co)))
+    dw = torch.empty(w_shape, dtype=torch.float32, device=device)
+    return dw, (B, H, W, Ci, Co, geom[5], geom[6], geom[11], geom[12], geom[9], geom[10], ptr(ws), ws.numel(), launch_flags(),
+                stream_ptr())
+
+
 def cl_wgrad(gr, gi, xr, xi, geom, w_shape, emul=None):
     """dW (float32, [Co, Ci, 3, 3] planes) from channels-last gradient / input planes (csrc/conv_cl_wgrad.hip)."""
-    B, Ci, Co, H, W = (geom[i] for i in range(5))
     gr, gi, xr, xi = (to_channels_last(t) for t in (gr, gi, xr, xi))
-    ws = _scratch(gr.device, int(_lib.load().cplxamd_conv2d_cl_wgrad_ws_bytes(B, H, W, Ci, Co)))
-    dwr = torch.empty(w_shape, dtype=torch.float32, device=gr.device)
+    dwr, tail = _cl_wgrad_args(geom, w_shape, gr.device)
     dwi = torch.empty_like(dwr)
-    call("cplxamd_conv2d_cl_wgrad_fl", ptr(gr), ptr(gi), ptr(xr), ptr(xi), ptr(emul), ptr(dwr), ptr(dwi), B, H, W, Ci, Co,
-         geom[5], geom[6], geom[11], geom[12], geom[9], geom[10], ptr(ws), ws.numel(), launch_flags(), stream_ptr())
+    call("cplxamd_conv2d_cl_wgrad_fl", ptr(gr), ptr(gi), ptr(xr), ptr(xi), ptr(emul), ptr(dwr), ptr(dwi), *tail)
     return dwr, dwi
 
 
@@ -223,17 +231,13 @@ def cl_wgrad_bn(gr, gi, zr, zi, coef, node):
     if not (node.needs_input_grad[2] or node.needs_input_grad[3]):
         return None
     xr, xi = node.saved_tensors[:2]
-    geom = node.geom
-    B, Ci, Co, H, W = (geom[i] for i in range(5))
-    if tuple(zr.shape) != tuple(gr.shape) or zr.shape[1] != Co:
+    if tuple(zr.shape) != tuple(gr.shape) or zr.shape[1] != node.geom[2]:
         return None
-    ws = _scratch(gr.device, int(_lib.load().cplxamd_conv2d_cl_wgrad_ws_bytes(B, H, W, Ci, Co)))
-    dyr, dyi = torch.empty_like(zr), torch.empty_like(zi)
-    dwr = torch.empty(node.wshape, dtype=torch.float32, device=gr.device)
+    dwr, tail = _cl_wgrad_args(node.geom, node.wshape, gr.device)
     dwi = torch.empty_like(dwr)
+    dyr, dyi = torch.empty_like(zr), torch.empty_like(zi)
     if not try_call("cplxamd_conv2d_cl_wgrad_bn_fl", ptr(gr), ptr(gi), ptr(zr), ptr(zi), ptr(coef), ptr(xr), ptr(xi), ptr(dyr),
-                    ptr(dyi), ptr(dwr), ptr(dwi), B, H, W, Ci, Co, geom[5], geom[6], geom[11], geom[12], geom[9], geom[10],
-                    ptr(ws), ws.numel(), launch_flags(), stream_ptr()):
+                    ptr(dyi), ptr(dwr), ptr(dwi), *tail):
         return None
     return dyr, dyi, (dwr, dwi, node)
 
@@ -279,13 +283,29 @@ class ToChannelsLastFn(torch.autograd.Function):
 
 
 def _cl_pack(wr, wi, dgrad):
-    """bf16 weight planes [Co, Ci, KH, KW] -> the per-stage LDS images of conv_cl.hip."""
+    """bf16 weight planes [Co, Ci, KH, KW] (wi None: real weights) -> the per-stage LDS images of conv_cl.hip."""
     Co, Ci, KH, KW = wr.shape
     N, C = (Ci, Co) if dgrad else (Co, Ci)
-    nbytes = int(_lib.load().cplxamd_conv2d_cl_pack_bytes(N, C, KH, KW))
+    kind, planes = ("clr", (wr,)) if wi is None else ("cl", (wr, wi))
+    nbytes = int(getattr(_lib.load(), "cplxamd_conv2d_%s_pack_bytes" % kind)(N, C, KH, KW))
     out = torch.empty(nbytes, dtype=torch.uint8, device=wr.device)
-    call("cplxamd_conv2d_cl_pack", ptr(wr), ptr(wi), ptr(out), Co, Ci, KH, KW, int(dgrad), stream_ptr())
+    call("cplxamd_conv2d_%s_pack" % kind, *(ptr(w) for w in planes), ptr(out), Co, Ci, KH, KW, int(dgrad), stream_ptr())
     return out
+
+
+def _cl_conv_args(x, geom, dgrad, real=False):
+    """What cl_conv and cl_conv_real marshal alike for the channels-last plane(s) like x: -> (an empty output plane, its
+    channel count N, the geometry arguments (B, H, W, C, N, KH, KW, dil_h, dil_w, pad_h, pad_w), the dump-scratch arguments
+    (pointer, bytes)).  cplxamd_conv2d_cl[r]_fl takes: planes, *geometry, mode, *scratch, flags, stream."""
+    B, Ci, Co, H, W, KH, KW = (geom[i] for i in range(7))
+    C, N = (Co, Ci) if dgrad else (Ci, Co)
+    Ho = H + 2 * geom[9] - geom[11] * (KH - 1)
+    Wo = W + 2 * geom[10] - geom[12] * (KW - 1)
+    oshape = (B, N, H, W) if dgrad else (B, N, Ho, Wo)
+    y = torch.empty(oshape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    ws_bytes = getattr(_lib.load(), "cplxamd_conv2d_clr_ws_bytes" if real else "cplxamd_conv2d_cl_ws_bytes")
+    ws = _scratch(x.device, int(ws_bytes(N)))
+    return y, N, (B, H, W, C, N, KH, KW, geom[11], geom[12], geom[9], geom[10]), (ptr(ws), ws.numel())
 
 
 # Convolutions whose output a training-mode batch-norm layer consumed recently (keyed by the weight parameter, weakly):
@@ -361,26 +381,19 @@ def cl_conv(xr, xi, wr, wi, br, bi, geom, dgrad=False, moments=False):
     conjugated, channel-swapped kernel) on channels-last planes; returns channels-last [B, N, H, W] tensors.
     moments (forward only): also leave the batch-norm moments of the output on it (ops.attach_moments) when the
     kernel variant takes the shape."""
-    B, Ci, Co, H, W, KH, KW = (geom[i] for i in range(7))
-    C, N = (Co, Ci) if dgrad else (Ci, Co)
     xr, xi = to_channels_last(xr), to_channels_last(xi)
     wp = _cl_pack(wr, wi, dgrad)
-    Ho = H + 2 * geom[9] - geom[11] * (KH - 1)
-    Wo = W + 2 * geom[10] - geom[12] * (KW - 1)
-    oshape = (B, N, H, W) if dgrad else (B, N, Ho, Wo)
-    yr = torch.empty(oshape, dtype=xr.dtype, device=xr.device, memory_format=torch.channels_last)
+    yr, N, geo, scratch = _cl_conv_args(xr, geom, dgrad)
     yi = torch.empty_like(yr)
-    ws = _scratch(xr.device, int(_lib.load().cplxamd_conv2d_cl_ws_bytes(N)))
     flags = launch_flags()          # one policy for the whole call (the moments variant and its chunk count must agree)
-    args = (ptr(xr), ptr(xi), ptr(wp), ptr(br), ptr(bi), ptr(yr), ptr(yi), B, H, W, C, N, KH, KW, geom[11], geom[12], geom[9],
-            geom[10], int(dgrad), ptr(ws), ws.numel(), flags, stream_ptr())
+    planes = (ptr(xr), ptr(xi), ptr(wp), ptr(br), ptr(bi), ptr(yr), ptr(yi))
+    args = (*planes, *geo, int(dgrad), *scratch, flags, stream_ptr())
     if moments and not dgrad and _CL_PATCH and _MOMENTS:
-        chunks = int(_lib.load().cplxamd_conv2d_cl2_mom_chunks_fl(B, H, W, C, N, KH, KW, geom[11], geom[12], geom[9], geom[10],
-                                                                  flags))
+        chunks = int(_lib.load().cplxamd_conv2d_cl2_mom_chunks_fl(*geo, flags))
         if chunks > 0:
             partials = torch.empty(chunks * N * 5, dtype=torch.float64, device=xr.device)
-            if try_call("cplxamd_conv2d_cl2_mom_fl", *args[:18], ptr(partials), partials.numel() * 8, ptr(ws), ws.numel(),
-                        flags, stream_ptr()):
+            if try_call("cplxamd_conv2d_cl2_mom_fl", *planes, *geo, ptr(partials), partials.numel() * 8, *scratch, flags,
+                        stream_ptr()):
                 ops.attach_moments(yr, yi, partials, chunks)
                 return yr, yi
     # dilation 1: the 2-d-patch kernel (activations staged once per channel slice for all nine taps); else the row kernel
@@ -413,31 +426,21 @@ def cl_conv_lrt_dx(gr, gi, wr, wi, geom, xr, xi, ga):
 
 
 def cl_conv_real(x, w, b, geom, dgrad=False):
-    """Real-valued cl_conv (csrc/conv_cl_real.hip): the variance path of the LRT layers and the real VD / ARD layers."""
-    B, Ci, Co, H, W, KH, KW = (geom[i] for i in range(7))
-    C, N = (Co, Ci) if dgrad else (Ci, Co)
+    """Real-valued cl_conv (the CPLX = false kernel of csrc/conv_cl.hip): the variance path of the LRT layers and the real
+    VD / ARD layers."""
     x = to_channels_last(x)
-    lib = _lib.load()
-    wp = torch.empty(int(lib.cplxamd_conv2d_clr_pack_bytes(N, C, KH, KW)), dtype=torch.uint8, device=x.device)
-    call("cplxamd_conv2d_clr_pack", ptr(w), ptr(wp), Co, Ci, KH, KW, int(dgrad), stream_ptr())
-    Ho = H + 2 * geom[9] - geom[11] * (KH - 1)
-    Wo = W + 2 * geom[10] - geom[12] * (KW - 1)
-    oshape = (B, N, H, W) if dgrad else (B, N, Ho, Wo)
-    y = torch.empty(oshape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    ws = _scratch(x.device, int(lib.cplxamd_conv2d_clr_ws_bytes(N)))
-    call("cplxamd_conv2d_clr_fl", ptr(x), ptr(wp), ptr(b), ptr(y), B, H, W, C, N, KH, KW, geom[11], geom[12], geom[9],
-         geom[10], int(dgrad), ptr(ws), ws.numel(), launch_flags(), stream_ptr())
+    wp = _cl_pack(w, None, dgrad)
+    y, _, geo, scratch = _cl_conv_args(x, geom, dgrad, real=True)
+    call("cplxamd_conv2d_clr_fl", ptr(x), ptr(wp), ptr(b), ptr(y), *geo, int(dgrad), *scratch, launch_flags(), stream_ptr())
     return y
 
 
 def cl_wgrad_real(g, x, geom, w_shape, emul=None, emul_exp=False):
-    """dW (float32 [Co, Ci, 3, 3]) = (sum g x) * emul (or * exp(emul)) from channels-last planes."""
-    B, Ci, Co, H, W = (geom[i] for i in range(5))
+    """dW (float32 [Co, Ci, 3, 3]) = (sum g x) * emul (or * exp(emul)) from channels-last planes (the CPLX = false kernel
+    of csrc/conv_cl_wgrad.hip)."""
     g, x = to_channels_last(g), to_channels_last(x)
-    ws = _scratch(g.device, int(_lib.load().cplxamd_conv2d_clr_wgrad_ws_bytes(B, H, W, Ci, Co)))
-    dw = torch.empty(w_shape, dtype=torch.float32, device=g.device)
-    call("cplxamd_conv2d_clr_wgrad_fl", ptr(g), ptr(x), ptr(emul), int(emul_exp), ptr(dw), B, H, W, Ci, Co, geom[5], geom[6],
-         geom[11], geom[12], geom[9], geom[10], ptr(ws), ws.numel(), launch_flags(), stream_ptr())
+    dw, tail = _cl_wgrad_args(geom, w_shape, g.device, real=True)
+    call("cplxamd_conv2d_clr_wgrad_fl", ptr(g), ptr(x), ptr(emul), int(emul_exp), ptr(dw), *tail)
     return dw
 
 

@@ -7,8 +7,10 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value"
 mkdir -p build
 pids=()
+objs=()     # only the objects of the sources that exist: build/ may hold what an earlier tree's sources left behind
 for f in *.hip; do
   o=build/${f%.hip}.o
+  objs+=("$o")
   stale=0
   # (the half-operand translation units are wrappers that #include a .hip source: that source is a dependency too)
   inc=$(sed -n 's/^#include "\(.*\.hip\)".*/\1/p' "$f")
@@ -21,5 +23,5 @@ for f in *.hip; do
   fi
 done
 for p in "${pids[@]}"; do wait $p; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC build/*.o -o $OUT
+$HIPCC --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o $OUT
 echo "built $(realpath $OUT)"

@@ -23,6 +23,11 @@
 //    stages later.
 //  * weights are pre-packed per (output-channel tile, stage) as the LDS image itself (csrc: pack_kernel), with
 //    the conjugate / flip / channel swap of the data gradient folded into the packing, so the kernel has one form.
+//
+// The same source is the REAL-valued kernel (CPLX = false): the variance path of the local-reparameterization
+// convolution layers (conv of |x|^2 with exp(log_sigma2), cplxmodule/nn/relevance/complex/base.py:120-135,
+// real/base.py:116-163) and the real Conv2dVD / ARD layers.  Everything the two variants differ in is derived from
+// CPLX in Geo below; the kernel, the packing and the launcher are written once in those terms.
 #include <type_traits>
 
 #include "common.h"
@@ -32,29 +37,46 @@
 namespace cplxamd {
 namespace cl {
 
-constexpr int NT = 512, TM = 512, BN = 64;
-constexpr int A_PLANE = TM * 32 + 64;        // 512 rows x 16 channels, then the zero row (row 512)
-constexpr int ZROW = TM * 32;                // plane-relative byte address of the zero row
-constexpr int NST = 16;                       // global stores per wave in the epilogue (2 planes x 2 blocks x 4 rounds)
+constexpr int NT = 512, BN = 64;
+constexpr int NST = 16;                       // global stores per wave in the epilogue (NP planes x IB blocks x 4 rounds)
 
-template <int KW> struct Geo {
+// What the complex and the real kernel differ in.  A complex block pair costs four MFMAs (re/im x re/im), a real one
+// a single MFMA, so the real wave takes twice the pixels for the same 128 accumulators and the same MFMAs per byte
+// staged: complex 2 planes x (2 x 2) blocks per wave, workgroup tile 512 grid pixels, 44 KiB per stage for 192 MFMAs per
+// wave; real 1 plane x (4 x 2) blocks, 1024 grid pixels, 38 KiB per stage for 96.
+template <int KW, bool CPLX> struct Geo {
+  static constexpr int NP = CPLX ? 2 : 1;                      // planes of every operand
+  static constexpr int IB = CPLX ? 2 : 4;                      // 32-pixel blocks per wave (x 2 blocks of 32 channels)
+  static constexpr int TM = 8 * 32 * IB;                       // grid pixels per workgroup tile (8 waves)
+  static constexpr int A_PLANE = TM * 32 + 64;                 // TM rows x 16 channels, then the zero row (row TM)
+  static constexpr int ZROW = TM * 32;                         // plane-relative byte address of the zero row
+  static constexpr int AP = TM * 32 / 8192;                    // LDS-DMA pieces (8 KiB per workgroup) of one A plane
+  static constexpr int NA = NP * AP;                           // ... of the activations: 4 either way
   static constexpr int W_PLANE = KW * 64 * 32;                 // [kw][64 co][16 ch] bf16
-  static constexpr int W_BYTES = 2 * W_PLANE;
-  static constexpr int STAGE = 2 * A_PLANE + W_BYTES;
-  static constexpr int PWN = (W_BYTES + 8191) / 8192;          // LDS-DMA pieces (8 KiB per workgroup) of the weights
-  static constexpr int L = 4 + PWN;                            // pieces per stage and wave
+  static constexpr int W_BYTES = NP * W_PLANE;
+  static constexpr int STAGE = NP * A_PLANE + W_BYTES;
+  static constexpr int PWN = (W_BYTES + 8191) / 8192;          // LDS-DMA pieces of the weights
+  static constexpr int W_BACK = W_BYTES / 16 < NT ? W_BYTES / 16 : NT;   // surplus lanes of the last weight piece re-read
+                                                               // the chunk this far back (a piece, or the whole image
+                                                               // when that is shorter) into the dump
+  static constexpr int L = NA + PWN;                           // pieces per stage and wave
+  static constexpr int GRP = IB * 2;                           // block pairs = MFMA groups per tap
+  static constexpr int MPG = NP * NP;                          // MFMAs per group
+  static constexpr int NRD = NP * (2 + IB);                    // fragment reads per tap: NP x (2 weight + IB activation)
+  static constexpr int RPG = (NRD + GRP - 1) / GRP;            // ... per group: 8 over 4 groups / 6 over the first 6 of 8
   static constexpr int EPI = 3 * STAGE;                        // per wave: 16 epilogue rows of 144 B, then 512 B of bias
   static constexpr int EPI_WAVE = 16 * 144 + 512;
   static constexpr int DUMP = EPI + 8 * EPI_WAVE;              // where the surplus half of a weight piece goes
   static constexpr int SMEM = DUMP + 4096;
 };
 
-struct Args {
-  const void* x_r; const void* x_i;          // [P][C] bf16
+template <bool CPLX> struct Args {
+  static constexpr int NP = CPLX ? 2 : 1;    // planes: real, imaginary
+  const void* x[NP];                         // [P][C] bf16
   const void* w;                             // packed weights (pack_kernel)
-  const float* bias_r; const float* bias_i;  // [Cout] or null
-  void* y_r; void* y_i;                      // [P][Cout] bf16
-  void* dump;                                // 512 x Cout bf16: where the rows a tile does not own are stored
+  const float* bias[NP];                     // [Cout] or null
+  void* y[NP];                               // [P][Cout] bf16
+  void* dump;                                // TM x Cout bf16: where the rows a tile does not own are stored
   int64_t P;
   uint32_t x_bytes, w_bytes;                 // bytes of one activation plane / of the packed weights
   int H, W, C, Cout, KH, dil_h, dil_w, pad_h, pad_w;   // H x W: the grid the tiles walk (the larger of the two images)
@@ -66,11 +88,11 @@ struct Args {
 
 enum { FL_NORMAL = 0, FL_FIRST0 = 1, FL_LAST = 2, FL_FIRST1 = 3 };
 
-template <int KW>
-__global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
+template <int KW, bool CPLX>
+__global__ __launch_bounds__(NT) void conv_cl_kernel(Args<CPLX> g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  using G = Geo<KW>;
-  constexpr int L = G::L, STAGE = G::STAGE;
+  using G = Geo<KW, CPLX>;
+  constexpr int L = G::L, STAGE = G::STAGE, NP = G::NP, IB = G::IB, AP = G::AP, A_PLANE = G::A_PLANE, ZROW = G::ZROW;
   static_assert(L + NST <= 63, "vmcnt is a 6-bit counter");
 
   const int ntiles = g.tiles_m * g.tiles_n;
@@ -88,15 +110,17 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
   const int tid0 = threadIdx.x;
   const int lane = tid0 & 63, wid = tid0 >> 6;
   const int l31 = lane & 31, lk = lane >> 5;
-  const int wm = wid * 64;
+  const int wm = wid * 32 * IB;
 
-  // zero rows (never overwritten: the A pieces cover rows 0..511 exactly)
-  if (tid0 < 96) {
-    const int slot = tid0 >> 5, r = tid0 & 31;
+  // zero rows, 16 dwords per slot and plane (never overwritten: the A pieces cover rows 0..TM-1 exactly)
+  if (tid0 < 3 * NP * 16) {
+    const int slot = tid0 / (NP * 16), r = tid0 % (NP * 16);
     *reinterpret_cast<uint32_t*>(smem + slot * STAGE + (r >> 4) * A_PLANE + ZROW + (r & 15) * 4) = 0u;
   }
 
-  const i32x4 rs_xr = make_rsrc(g.x_r, g.x_bytes), rs_xi = make_rsrc(g.x_i, g.x_bytes);
+  // (the plane arrays of Args are read at constant indices only: a subscript that is a loop counter, even of an unrolled
+  //  loop, keeps the whole argument block from being split into scalars up front)
+  const i32x4 rs_xr = make_rsrc(g.x[0], g.x_bytes), rs_xi = make_rsrc(g.x[NP - 1], g.x_bytes);
   const i32x4 rs_w = make_rsrc(g.w, g.w_bytes);
   const uint32_t rowbytes = (uint32_t)g.C * 2u;
 
@@ -107,16 +131,16 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
   // per-lane source offsets of the LDS-DMA pieces.  A plane: chunk p = j*512 + tid sits at LDS row p >> 1, position
   // p & 1, and holds channel half (p & 1) ^ ((row >> 3) & 1) of input row `row` of the window (so that the 16 lanes
   // of a ds_read_b128 group hit 16 distinct 16-byte bank groups).  Weights: the packed stage IS the LDS image.
-  uint32_t voa[2], vow[G::PWN];
+  uint32_t voa[AP], vow[G::PWN];
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
+  for (int j = 0; j < AP; ++j) {
     const int p = j * NT + tid0, row = p >> 1, c = (p & 1) ^ ((row >> 3) & 1);
     voa[j] = (uint32_t)row * rowbytes + (uint32_t)c * 16u;
   }
 #pragma unroll
   for (int j = 0; j < G::PWN; ++j) {
     int p = j * NT + tid0;
-    if (p >= G::W_BYTES / 16) p -= NT;                     // surplus lanes re-read the previous piece into the dump
+    if (p >= G::W_BYTES / 16) p -= G::W_BACK;              // surplus lanes re-read valid chunks into the dump
     vow[j] = (uint32_t)p * 16u;
   }
 
@@ -125,10 +149,10 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
   // same coordinates in the dense input -- no longer window start + row, so the lane offsets are rebuilt per tile
   // (two divisions per piece).  Pixels outside the input alias others or fall out of range; the fragment masks skip them.
   const bool in_dense = g.Hi == g.H && g.Wi == g.W;
-  uint32_t voa_c[2], voa_n[2];                     // offsets of the tile the LDS-DMA pointer is in / of the one after it
-  auto lane_offsets = [&](int rr, uint32_t (&out)[2]) __attribute__((always_inline)) {
+  uint32_t voa_c[AP], voa_n[AP];                   // offsets of the tile the LDS-DMA pointer is in / of the one after it
+  auto lane_offsets = [&](int rr, uint32_t (&out)[AP]) __attribute__((always_inline)) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
+    for (int j = 0; j < AP; ++j) {
       if (in_dense) { out[j] = voa[j]; continue; }
       const int pr = j * NT + tid0, row = pr >> 1, c = (pr & 1) ^ ((row >> 3) & 1);
       // (the kernel-row part of the shift stays in the scalar offset: it may turn a row that starts above the image,
@@ -145,9 +169,9 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
   };
 
   // fragment addresses relative to the slot.  x: row = wm + i*32 + l31 + kw*dil_w; w: co = j*32 + l31.
-  uint32_t a_rel[2][KW], w_rel[2];
+  uint32_t a_rel[IB][KW], w_rel[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < IB; ++i)
 #pragma unroll
     for (int kw = 0; kw < KW; ++kw) {
       const int row = wm + i * 32 + l31 + kw * g.dil_w;
@@ -156,11 +180,12 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int co = j * 32 + l31;
-    w_rel[j] = (uint32_t)(2 * A_PLANE + co * 32 + ((lk ^ ((co >> 3) & 1)) << 4));
+    w_rel[j] = (uint32_t)(NP * A_PLANE + co * 32 + ((lk ^ ((co >> 3) & 1)) << 4));
   }
 
-  f32x16 acc_r[2][2], acc_i[2][2];
-  bf16x8 ar[2][2], ai[2][2], br[2][2], bi[2][2];           // [set][block]
+  // (one array per plane, not [NP]: the imaginary ones are simply never touched by the real kernel and vanish)
+  f32x16 acc_r[IB][2], acc_i[IB][2];                       // [pixel block][channel block]
+  bf16x8 ar[2][IB], ai[2][IB], br[2][2], bi[2][2];         // [set][block]
 
   // ---- tiles -------------------------------------------------------------------------------------------------
   int v = blockIdx.x;
@@ -187,29 +212,32 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
       d_u = 0; d_cs = 0;
       d_aoff = a_origin(r0n);
       d_woff = (uint32_t)(ntn * g.NS) * (uint32_t)G::W_BYTES;
-      voa_c[0] = voa_n[0]; voa_c[1] = voa_n[1];
+#pragma unroll
+      for (int j = 0; j < AP; ++j) voa_c[j] = voa_n[j];
     }
   };
   const uint32_t soff[3] = {smem_off, smem_off + (uint32_t)STAGE, smem_off + 2u * (uint32_t)STAGE};
   // piece q of the stage at the pointer -> slot
   auto dma_piece = [&](int q, uint32_t slot_off) __attribute__((always_inline)) {
-    if (q < 2) buf_lds16_soff(rs_xr, voa_c[q] + d_aoff, 0u, slot_off + (uint32_t)(q * 8192) + wave_lds);
-    else if (q < 4) buf_lds16_soff(rs_xi, voa_c[q - 2] + d_aoff, 0u, slot_off + (uint32_t)(A_PLANE + (q - 2) * 8192) + wave_lds);
+    // AP pieces of the real plane, (CPLX) AP of the imaginary one, then the weights
+    if (q < AP) buf_lds16_soff(rs_xr, voa_c[q] + d_aoff, 0u, slot_off + (uint32_t)(q * 8192) + wave_lds);
+    else if (q < G::NA)
+      buf_lds16_soff(rs_xi, voa_c[q - AP] + d_aoff, 0u, slot_off + (uint32_t)(A_PLANE + (q - AP) * 8192) + wave_lds);
     else {
-      const int j = q - 4;
+      const int j = q - G::NA;
       constexpr int FULLW = G::W_BYTES / 1024;             // waves of weight data in total
       const bool real = (uint32_t)(j * 8) + wid_u < (uint32_t)FULLW;
-      const uint32_t dst = real ? slot_off + (uint32_t)(2 * A_PLANE + j * 8192) + wave_lds
+      const uint32_t dst = real ? slot_off + (uint32_t)(NP * A_PLANE + j * 8192) + wave_lds
                                 : smem_off + (uint32_t)G::DUMP + (wave_lds & 4095u);
       buf_lds16_soff(rs_w, vow[j], d_woff, dst);
     }
   };
 
   // ---- masks: bit kw = column tap kw stays inside the image row, bit 8 + kh = row tap kh stays inside the image
-  uint32_t vmask[2];
+  uint32_t vmask[IB];
   auto tile_masks = [&]() __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < IB; ++i) {
       const uint32_t q = (uint32_t)(r0 + wm + i * 32 + l31);
       const uint32_t qh = fast_div(q, g.div_w), w = q - qh * (uint32_t)g.W;
       const uint32_t h = qh - fast_div(qh, g.div_h) * (uint32_t)g.H;
@@ -234,43 +262,52 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
     return (a_rel[i][kw] & m) | ((uint32_t)ZROW & ~m);
   };
 
-  // fragment idx of tap kw of the stage in slot `sl` -> register set `st` (idx order: what the first MFMA group needs first)
+  // fragment idx of tap kw of the stage in slot `sl` -> register set `st`: the NP planes of the fragments in the order
+  // w 0, x 0, w 1, x 1, (x 2, x 3) -- what the first MFMA groups need first
   auto read_one = [&](int st, const char* sl, int kw, int kh, int idx) __attribute__((always_inline)) {
+    const int f = idx / NP;
+    const bool im = idx % NP;
     const char* wr_ = sl + kw * 2048;
     const char* wi_ = wr_ + G::W_PLANE;
-    if (idx == 0) br[st][0] = *reinterpret_cast<const bf16x8*>(wr_ + w_rel[0]);
-    else if (idx == 1) bi[st][0] = *reinterpret_cast<const bf16x8*>(wi_ + w_rel[0]);
-    else if (idx == 2) ar[st][0] = *reinterpret_cast<const bf16x8*>(sl + masked(0, kw, kh));
-    else if (idx == 3) ai[st][0] = *reinterpret_cast<const bf16x8*>(sl + A_PLANE + masked(0, kw, kh));
-    else if (idx == 4) br[st][1] = *reinterpret_cast<const bf16x8*>(wr_ + w_rel[1]);
-    else if (idx == 5) bi[st][1] = *reinterpret_cast<const bf16x8*>(wi_ + w_rel[1]);
-    else if (idx == 6) ar[st][1] = *reinterpret_cast<const bf16x8*>(sl + masked(1, kw, kh));
-    else ai[st][1] = *reinterpret_cast<const bf16x8*>(sl + A_PLANE + masked(1, kw, kh));
+    if (f == 0 || f == 2) {
+      if (!im) br[st][f >> 1] = *reinterpret_cast<const bf16x8*>(wr_ + w_rel[f >> 1]);
+      else bi[st][f >> 1] = *reinterpret_cast<const bf16x8*>(wi_ + w_rel[f >> 1]);
+    } else {
+      const int i = f == 1 ? 0 : f - 2;
+      if (!im) ar[st][i] = *reinterpret_cast<const bf16x8*>(sl + masked(i, kw, kh));
+      else ai[st][i] = *reinterpret_cast<const bf16x8*>(sl + A_PLANE + masked(i, kw, kh));
+    }
   };
 
-  // 16 MFMAs on register set `st`; behind group n two fragment reads of (slot rs_, tap rkw, kernel row rkh) into
-  // the other set and, behind groups 1 and 3, the LDS-DMA pieces [q0, q1) of the stage at the pointer -> slot ds
+  // GRP groups of MPG MFMAs on register set `st`; behind group n its RPG fragment reads of (slot rsl, tap rkw, kernel
+  // row rkh) into the other set (NRD in all) and the LDS-DMA pieces [q0, q1) of the stage at the pointer -> slot ds,
+  // spread over the groups
   auto mfma_sub = [&](int st, const char* rsl, int rkw, int rkh, bool do_read, uint32_t ds, int q0, int q1)
       __attribute__((always_inline)) {
-    bf16x8 nai[2];
+    bf16x8 nai[IB];
     int q = q0;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < IB; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        if (j == 0) nai[i] = neg_frag(ai[st][i]);          // (not earlier: block 1's fragments were read last)
-        acc_r[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(br[st][j], ar[st][i], acc_r[i][j], 0, 0, 0);
-        acc_i[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(br[st][j], ai[st][i], acc_i[i][j], 0, 0, 0);
-        acc_r[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bi[st][j], nai[i], acc_r[i][j], 0, 0, 0);
-        acc_i[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bi[st][j], ar[st][i], acc_i[i][j], 0, 0, 0);
+        if constexpr (CPLX) {
+          if (j == 0) nai[i] = neg_frag(ai[st][i]);        // (not earlier: block 1's fragments were read last)
+          acc_r[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(br[st][j], ar[st][i], acc_r[i][j], 0, 0, 0);
+          acc_i[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(br[st][j], ai[st][i], acc_i[i][j], 0, 0, 0);
+          acc_r[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bi[st][j], nai[i], acc_r[i][j], 0, 0, 0);
+          acc_i[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bi[st][j], ar[st][i], acc_i[i][j], 0, 0, 0);
+        } else {
+          acc_r[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(br[st][j], ar[st][i], acc_r[i][j], 0, 0, 0);
+        }
         const int grp = i * 2 + j;
         __builtin_amdgcn_sched_barrier(0);
         if (do_read) {
-          read_one(st ^ 1, rsl, rkw, rkh, 2 * grp);
-          read_one(st ^ 1, rsl, rkw, rkh, 2 * grp + 1);
+#pragma unroll
+          for (int r = 0; r < G::RPG; ++r)
+            if (G::RPG * grp + r < G::NRD) read_one(st ^ 1, rsl, rkw, rkh, G::RPG * grp + r);
         }
         __builtin_amdgcn_sched_barrier(0);
-        const int left = 4 - grp;
+        const int left = G::GRP - grp;
         const int n_now = (q1 - q + left - 1) / left;
 #pragma unroll
         for (int r = 0; r < 6; ++r)
@@ -299,8 +336,8 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
       mfma_sub(par, p0, 1, kh, true, o2, 0, 0);
       mfma_sub(par ^ 1, p0, 2, kh, true, o2, 0, 0);
     } else {
-      mfma_sub(par, p0, 1, kh, true, o2, 2, 4);
-      mfma_sub(par ^ 1, p0, 2, kh, true, o2, 4, L);
+      mfma_sub(par, p0, 1, kh, true, o2, 2, G::NA);
+      mfma_sub(par ^ 1, p0, 2, kh, true, o2, G::NA, L);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     // (FIRST0 / FIRST1: the stages they need landed before the stores' wait; a plain vmcnt(L) would wait for the
@@ -330,12 +367,12 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
   auto epilogue = [&](int nt_) __attribute__((always_inline)) {
     const int t = opaque_tid();
     const int ln = t & 63, w_ = t >> 6, q31 = ln & 31, qk = ln >> 5;
-    const int wm_ = w_ * 64;
+    const int wm_ = w_ * 32 * IB;
     char* reg = smem + G::EPI + w_ * G::EPI_WAVE;
     constexpr int PITCH = 144;
     const int r16 = q31 >> 4, rr = q31 & 15;
     const int64_t ldc = g.Cout;
-    const bool out_dense = g.Ho == g.H && g.Wo == g.W, wide = g.W >= 64;
+    const bool out_dense = g.Ho == g.H && g.Wo == g.W, wide = g.W >= 32 * IB;
     uint32_t w_first = 0, h_first = 0, b_first = 0;       // grid coordinates of this lane's first row (r0 + wm + lane / 8)
     if (!out_dense) {
       const uint32_t q = (uint32_t)(r0 + wm_ + (ln >> 3)), qh = fast_div(q, g.div_w);
@@ -344,10 +381,10 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
     int64_t own = g.P - r0;
     if (own > g.tm_out) own = g.tm_out;
 #pragma unroll
-    for (int pl = 0; pl < 2; ++pl) {
-      bf16_t* out = reinterpret_cast<bf16_t*>(pl ? g.y_i : g.y_r);
+    for (int pl = 0; pl < NP; ++pl) {
+      bf16_t* out = reinterpret_cast<bf16_t*>(pl ? g.y[NP - 1] : g.y[0]);
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < IB; ++i)
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
           if (r16 == half) {
@@ -371,7 +408,7 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
             bool ok = m < own;
             if (!out_dense) {                       // output image smaller than the grid: its own dense row index
               uint32_t w = w_first + (uint32_t)(i * 32 + half * 16 + sub * 8), h = h_first, b = b_first;
-              if (wide) {                           // (W >= 64: one carry at most for the 64 rows of a wave)
+              if (wide) {                           // (one carry at most for the 32 IB rows of a wave)
                 if (w >= (uint32_t)g.W) { w -= (uint32_t)g.W; if (++h == (uint32_t)g.H) { h = 0; ++b; } }
               } else {
                 const uint32_t q = (uint32_t)orow, qh = fast_div(q, g.div_w);
@@ -390,14 +427,15 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
     }
   };
 
-  // bias of column tile nt_ -> this wave's 512 bytes behind its epilogue rows (lanes 0-15 real, 16-31 imaginary)
+  // bias of column tile nt_ -> this wave's 512 bytes behind its epilogue rows (16 lanes per plane)
   const uint32_t bias_lds = smem_off + (uint32_t)G::EPI + wid_u * (uint32_t)G::EPI_WAVE + 2304u;
   auto bias_dma = [&](int nt_) __attribute__((always_inline)) {
     const int t = opaque_tid();
     const int ln = t & 63;
-    if (ln < 32) {
-      const float* src = g.bias_r ? ((ln < 16 ? g.bias_r : g.bias_i) + nt_ * BN + 4 * (ln & 15))
-                                  : reinterpret_cast<const float*>(g.w) + 4 * ln;
+    if (ln < 16 * NP) {
+      const float* src = g.bias[0] ? (CPLX ? (ln < 16 ? g.bias[0] : g.bias[NP - 1]) + nt_ * BN + 4 * (ln & 15)
+                                           : g.bias[0] + nt_ * BN + 4 * ln)
+                                   : reinterpret_cast<const float*>(g.w) + 4 * ln;
       lds_dma16_at(src, bias_lds);
     }
   };
@@ -406,25 +444,25 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
     const int w_ = t >> 6, qk = (t & 63) >> 5;
     const char* breg = smem + G::EPI + w_ * G::EPI_WAVE + 2304;
 #pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
+    for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          f4 b = {{0.f, 0.f, 0.f, 0.f}};
-          if (g.bias_r) b = ld4(reinterpret_cast<const float*>(breg + pl * 256 + (j * 32 + 8 * q + 4 * qk) * 4));
+          f4 bv = {{0.f, 0.f, 0.f, 0.f}};
+          if (g.bias[0]) bv = ld4(reinterpret_cast<const float*>(breg + pl * 256 + (j * 32 + 8 * q + 4 * qk) * 4));
 #pragma unroll
-          for (int i = 0; i < 2; ++i)
+          for (int i = 0; i < IB; ++i)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              if (pl) acc_i[i][j][4 * q + e] = b.v[e];
-              else acc_r[i][j][4 * q + e] = b.v[e];
+              if (pl) acc_i[i][j][4 * q + e] = bv.v[e];
+              else acc_r[i][j][4 * q + e] = bv.v[e];
             }
         }
   };
   auto first_frags = [&]() __attribute__((always_inline)) {
 #pragma unroll
-    for (int idx = 0; idx < 8; ++idx) read_one(0, sbase[0], 0, 0, idx);
+    for (int idx = 0; idx < G::NRD; ++idx) read_one(0, sbase[0], 0, 0, idx);
   };
 
   // start stagger: tiles take the same time on every CU, so without it all 256 CUs reach their epilogues together
@@ -480,8 +518,10 @@ __global__ __launch_bounds__(NT) void conv_cl_kernel(Args g) {
 // ---- weight packing: [Co][Ci][KH][KW] planes (bf16) -> per (column tile, kernel row, 16-channel slice) the LDS image
 // [plane][kw][64 n][2 chunk positions][8] with chunk position cp holding channel half cp ^ ((n >> 3) & 1).
 // dgrad: n runs over Ci, the contraction over Co, both kernel axes flipped, imaginary plane negated (conj).
-__global__ void pack_kernel(const bf16_t* w_r, const bf16_t* w_i, bf16_t* out, int Co, int Ci, int KH, int KW,
-                            int dgrad, int64_t total) {
+// (w_i: unused by the real kernel)
+template <bool CPLX>
+__global__ void pack_kernel(const bf16_t* w_r, const bf16_t* w_i, bf16_t* out, int Co, int Ci, int KH, int KW, int dgrad,
+                            int64_t total) {
   const int N = dgrad ? Ci : Co, C = dgrad ? Co : Ci;
   const int C16 = C / 16;
   for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (int64_t)gridDim.x * blockDim.x) {
@@ -490,7 +530,8 @@ __global__ void pack_kernel(const bf16_t* w_r, const bf16_t* w_i, bf16_t* out, i
     const int cp = (int)(t & 1); t >>= 1;
     const int nl = (int)(t & 63); t >>= 6;
     const int kw = (int)(t % KW); t /= KW;
-    const int pl = (int)(t & 1); t >>= 1;
+    int pl = 0;
+    if constexpr (CPLX) { pl = (int)(t & 1); t >>= 1; }
     const int cs = (int)(t % C16); t /= C16;
     const int kh = (int)(t % KH); t /= KH;
     const int nt = (int)t;
@@ -498,11 +539,12 @@ __global__ void pack_kernel(const bf16_t* w_r, const bf16_t* w_i, bf16_t* out, i
     const int c = cs * 16 + ((cp ^ ((nl >> 3) & 1)) << 3) + e;
     bf16_t val = 0;
     if (n < N) {
-      const bf16_t* src = pl ? w_i : w_r;
+      const bf16_t* src = CPLX && pl ? w_i : w_r;
       if (!dgrad) val = src[(((int64_t)n * Ci + c) * KH + kh) * KW + kw];
       else {
         val = src[(((int64_t)c * Ci + n) * KH + (KH - 1 - kh)) * KW + (KW - 1 - kw)];
-        if (pl) val ^= 0x8000u;
+        if constexpr (CPLX)
+          if (pl) val ^= 0x8000u;
       }
     }
     out[o] = val;
@@ -543,6 +585,88 @@ __global__ __launch_bounds__(256) void cl_to_nchw_kernel(const bf16_t* __restric
 
 using namespace cplxamd;
 
+// ---- the complex (cl) and the real (clr) entry points: one body each, instantiated twice --------------------------
+
+template <bool CPLX> static int64_t cl_pack_bytes(int N, int C, int KH, int KW) {
+  if (N <= 0 || C <= 0 || KH <= 0 || KW <= 0 || C % 16) return 0;
+  return (int64_t)((N + 63) / 64) * KH * (C / 16) * (CPLX ? 2 : 1) * KW * 64 * 16 * 2;
+}
+template <bool CPLX> static int64_t cl_ws_bytes(int Cout) {
+  return Cout > 0 ? (int64_t)cl::Geo<3, CPLX>::TM * Cout * 2 : 0;
+}
+
+template <bool CPLX>
+static int cl_pack(const void* w_r, const void* w_i, void* out, int Co, int Ci, int KH, int KW, int dgrad, void* stream) {
+  if (!w_r || (CPLX && !w_i) || !out || Co <= 0 || Ci <= 0 || KH <= 0 || KW <= 0) return CPLXAMD_EINVAL;
+  if ((dgrad ? Co : Ci) % 16) return CPLXAMD_ESHAPE;
+  const int64_t total = cl_pack_bytes<CPLX>(dgrad ? Ci : Co, dgrad ? Co : Ci, KH, KW) / 2;
+  cl::pack_kernel<CPLX><<<stream_grid(total, 256), 256, 0, (hipStream_t)stream>>>(
+      (const bf16_t*)w_r, (const bf16_t*)w_i, (bf16_t*)out, Co, Ci, KH, KW, dgrad, total);
+  CPLXAMD_CHECK_LAUNCH();
+  return 0;
+}
+
+// x, bias, y: the real plane, then (CPLX) the imaginary one
+template <bool CPLX>
+static int cl_launch(const void* const (&x)[2], const void* w_packed, const float* const (&bias)[2], void* const (&y)[2],
+                     int64_t B, int H, int W, int C, int N, int KH, int KW, int dil_h, int dil_w, int pad_h, int pad_w, int mode,
+                     void* ws, int64_t ws_bytes, int flags, void* stream) {
+  using G3 = cl::Geo<3, CPLX>;
+  constexpr int NP = G3::NP, TM = G3::TM;
+  if (!launch_flags_ok(flags)) return CPLXAMD_EINVAL;
+  if (!w_packed || B < 0 || H <= 0 || W <= 0 || C <= 0 || N <= 0 || KH <= 0 || KW <= 0 || dil_h <= 0 || dil_w <= 0 ||
+      pad_h < 0 || pad_w < 0 || (mode != 0 && mode != 1))
+    return CPLXAMD_EINVAL;
+  for (int pl = 0; pl < NP; ++pl)
+    if (!x[pl] || !y[pl] || (bias[pl] == nullptr) != (bias[0] == nullptr)) return CPLXAMD_EINVAL;
+  const int Hs = H + 2 * pad_h - dil_h * (KH - 1), Ws = W + 2 * pad_w - dil_w * (KW - 1);   // the smaller image
+  if (KW != 3 || C % 16 || N % 64 || (KH * (C / 16)) % 6 || Hs <= 0 || Ws <= 0 || Hs > H || Ws > W ||
+      (KW - 1) * dil_w > 64 || KH > 8)
+    return CPLXAMD_ESHAPE;
+  const int64_t P = B * H * W;
+  if (P == 0) return 0;
+  const int64_t halo = ((int64_t)dil_h * (KH - 1) * W + dil_w * (KW - 1) + TM) * C * 2;
+  if (P >= ((int64_t)1 << 31) - TM || P * C * 2 + 2 * halo >= (int64_t)0xF0000000) return CPLXAMD_ESHAPE;
+  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  if (!a16(w_packed) || !a16(ws)) return CPLXAMD_EALIGN;
+  for (int pl = 0; pl < NP; ++pl)
+    if (!a16(x[pl]) || !a16(y[pl]) || !a16(bias[pl])) return CPLXAMD_EALIGN;
+  if (!ws || ws_bytes < cl_ws_bytes<CPLX>(N)) return CPLXAMD_EINVAL;
+  cl::Args<CPLX> g{};
+  for (int pl = 0; pl < NP; ++pl) { g.x[pl] = x[pl]; g.bias[pl] = bias[pl]; g.y[pl] = y[pl]; }
+  g.w = w_packed; g.dump = ws;
+  g.P = P;
+  g.Hi = mode ? Hs : H; g.Wi = mode ? Ws : W; g.Ho = mode ? H : Hs; g.Wo = mode ? W : Ws;
+  g.x_bytes = (uint32_t)(B * g.Hi * g.Wi * C * 2);
+  if (mode) { pad_h = dil_h * (KH - 1) - pad_h; pad_w = dil_w * (KW - 1) - pad_w; }
+  g.w_bytes = (uint32_t)cl_pack_bytes<CPLX>(N, C, KH, KW);
+  g.H = H; g.W = W; g.C = C; g.Cout = N; g.KH = KH; g.dil_h = dil_h; g.dil_w = dil_w; g.pad_h = pad_h; g.pad_w = pad_w;
+  g.C16 = C / 16; g.NS = KH * g.C16;
+  g.tm_out = TM - (KW - 1) * dil_w;
+  g.tiles_m = (int)((P + g.tm_out - 1) / g.tm_out);
+  g.tiles_n = N / 64;
+  g.div_w = make_div((uint32_t)W); g.div_h = make_div((uint32_t)H);
+  const int ncu = device_cus() & ~7;
+  const int64_t ntiles = (int64_t)g.tiles_m * g.tiles_n;
+  if (ntiles > 0x7fffffff) return CPLXAMD_ESHAPE;
+  // chip shared with RCCL collectives (CPLXAMD_LAUNCH_SHARED, launch.h): one workgroup per tile
+  int grid = (ntiles < ncu || !launch_owns_chip(flags)) ? (int)ntiles : ncu;
+  // Start stagger.  A tile takes ~ NS stages x 2 waves per SIMD x (3 taps x GRP x MPG) MFMAs x 32 clocks / 0.5; the
+  // workgroups that get one tile less than the longest ones (ntiles % grid != 0) have that much slack: their starts are
+  // spread over it.
+  g.stagger = 0; g.stagger_from = 0;
+  if (ntiles > 2 * grid && ntiles % grid) {
+    const int64_t tile_clk = (int64_t)g.NS * 2 * (3 * G3::GRP * G3::MPG) * 32 * 2;
+    g.stagger_from = (int)(ntiles % grid);
+    g.stagger = (int)(tile_clk / (grid - g.stagger_from));
+  }
+  static PerDeviceOnce attr_set;
+  if (const int e = set_max_dyn_lds(attr_set, cl::conv_cl_kernel<3, CPLX>, G3::SMEM)) return e;
+  cl::conv_cl_kernel<3, CPLX><<<dim3((unsigned)grid), cl::NT, G3::SMEM, (hipStream_t)stream>>>(g);
+  CPLXAMD_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" {
 
 int cplxamd_cl_to_nchw(const void* x_cl, void* out, int64_t B, int C, int64_t S, void* stream) {
@@ -556,22 +680,17 @@ int cplxamd_cl_to_nchw(const void* x_cl, void* out, int64_t B, int C, int64_t S,
   return 0;
 }
 
-int64_t cplxamd_conv2d_cl_pack_bytes(int N, int C, int KH, int KW) {
-  if (N <= 0 || C <= 0 || KH <= 0 || KW <= 0 || C % 16) return 0;
-  return (int64_t)((N + 63) / 64) * KH * (C / 16) * 2 * KW * 64 * 16 * 2;
-}
-
-int64_t cplxamd_conv2d_cl_ws_bytes(int Cout) { return Cout > 0 ? (int64_t)cl::TM * Cout * 2 : 0; }
+int64_t cplxamd_conv2d_cl_pack_bytes(int N, int C, int KH, int KW) { return cl_pack_bytes<true>(N, C, KH, KW); }
+int64_t cplxamd_conv2d_clr_pack_bytes(int N, int C, int KH, int KW) { return cl_pack_bytes<false>(N, C, KH, KW); }
+int64_t cplxamd_conv2d_cl_ws_bytes(int Cout) { return cl_ws_bytes<true>(Cout); }
+int64_t cplxamd_conv2d_clr_ws_bytes(int Cout) { return cl_ws_bytes<false>(Cout); }
 
 int cplxamd_conv2d_cl_pack(const void* w_r, const void* w_i, void* out, int Co, int Ci, int KH, int KW, int dgrad,
                            void* stream) {
-  if (!w_r || !w_i || !out || Co <= 0 || Ci <= 0 || KH <= 0 || KW <= 0) return CPLXAMD_EINVAL;
-  if ((dgrad ? Co : Ci) % 16) return CPLXAMD_ESHAPE;
-  const int64_t total = cplxamd_conv2d_cl_pack_bytes(dgrad ? Ci : Co, dgrad ? Co : Ci, KH, KW) / 2;
-  cl::pack_kernel<<<stream_grid(total, 256), 256, 0, (hipStream_t)stream>>>(
-      (const bf16_t*)w_r, (const bf16_t*)w_i, (bf16_t*)out, Co, Ci, KH, KW, dgrad, total);
-  CPLXAMD_CHECK_LAUNCH();
-  return 0;
+  return cl_pack<true>(w_r, w_i, out, Co, Ci, KH, KW, dgrad, stream);
+}
+int cplxamd_conv2d_clr_pack(const void* w, void* out, int Co, int Ci, int KH, int KW, int dgrad, void* stream) {
+  return cl_pack<false>(w, nullptr, out, Co, Ci, KH, KW, dgrad, stream);
 }
 
 // Forward (mode 0):  y[b, ho, wo, n] = bias[n] + sum_{kh, kw, c} x[b, ho + kh dil_h - pad_h, wo + kw dil_w - pad_w, c] w[n, c, kh, kw]
@@ -589,55 +708,23 @@ int cplxamd_conv2d_cl(const void* x_r, const void* x_i, const void* w_packed, co
 int cplxamd_conv2d_cl_fl(const void* x_r, const void* x_i, const void* w_packed, const float* bias_r, const float* bias_i,
                          void* y_r, void* y_i, int64_t B, int H, int W, int C, int N, int KH, int KW, int dil_h, int dil_w,
                          int pad_h, int pad_w, int mode, void* ws, int64_t ws_bytes, int flags, void* stream) {
-  if (!launch_flags_ok(flags)) return CPLXAMD_EINVAL;
-  if (!x_r || !x_i || !w_packed || !y_r || !y_i || B < 0 || H <= 0 || W <= 0 || C <= 0 || N <= 0 || KH <= 0 ||
-      KW <= 0 || dil_h <= 0 || dil_w <= 0 || pad_h < 0 || pad_w < 0 || (bias_r == nullptr) != (bias_i == nullptr) ||
-      (mode != 0 && mode != 1))
-    return CPLXAMD_EINVAL;
-  const int Hs = H + 2 * pad_h - dil_h * (KH - 1), Ws = W + 2 * pad_w - dil_w * (KW - 1);   // the smaller image
-  if (KW != 3 || C % 16 || N % 64 || (KH * (C / 16)) % 6 || Hs <= 0 || Ws <= 0 || Hs > H || Ws > W ||
-      (KW - 1) * dil_w > 64 || KH > 8)
-    return CPLXAMD_ESHAPE;
-  const int64_t P = B * H * W;
-  if (P == 0) return 0;
-  const int64_t halo = ((int64_t)dil_h * (KH - 1) * W + dil_w * (KW - 1) + cl::TM) * C * 2;
-  if (P >= ((int64_t)1 << 31) - cl::TM || P * C * 2 + 2 * halo >= (int64_t)0xF0000000) return CPLXAMD_ESHAPE;
-  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (!a16(x_r) || !a16(x_i) || !a16(w_packed) || !a16(y_r) || !a16(y_i) || !a16(ws) || (bias_r && (!a16(bias_r) || !a16(bias_i))))
-    return CPLXAMD_EALIGN;
-  if (!ws || ws_bytes < cplxamd_conv2d_cl_ws_bytes(N)) return CPLXAMD_EINVAL;
-  cl::Args g{};
-  g.x_r = x_r; g.x_i = x_i; g.w = w_packed; g.bias_r = bias_r; g.bias_i = bias_i; g.y_r = y_r; g.y_i = y_i; g.dump = ws;
-  g.P = P;
-  g.Hi = mode ? Hs : H; g.Wi = mode ? Ws : W; g.Ho = mode ? H : Hs; g.Wo = mode ? W : Ws;
-  g.x_bytes = (uint32_t)(B * g.Hi * g.Wi * C * 2);
-  if (mode) { pad_h = dil_h * (KH - 1) - pad_h; pad_w = dil_w * (KW - 1) - pad_w; }
-  g.w_bytes = (uint32_t)cplxamd_conv2d_cl_pack_bytes(N, C, KH, KW);
-  g.H = H; g.W = W; g.C = C; g.Cout = N; g.KH = KH; g.dil_h = dil_h; g.dil_w = dil_w; g.pad_h = pad_h; g.pad_w = pad_w;
-  g.C16 = C / 16; g.NS = KH * g.C16;
-  g.tm_out = cl::TM - (KW - 1) * dil_w;
-  g.tiles_m = (int)((P + g.tm_out - 1) / g.tm_out);
-  g.tiles_n = N / 64;
-  g.div_w = make_div((uint32_t)W); g.div_h = make_div((uint32_t)H);
-  const int ncu = device_cus() & ~7;
-  const int64_t ntiles = (int64_t)g.tiles_m * g.tiles_n;
-  if (ntiles > 0x7fffffff) return CPLXAMD_ESHAPE;
-  // chip shared with RCCL collectives (CPLXAMD_LAUNCH_SHARED, launch.h): one workgroup per tile
-  int grid = (ntiles < ncu || !launch_owns_chip(flags)) ? (int)ntiles : ncu;
-  // Start stagger.  A tile takes ~ NS stages x 2 waves per SIMD x 48 MFMAs x 32 clocks / 0.5; the workgroups that get
-  // one tile less than the longest ones (ntiles % grid != 0) have that much slack: their starts are spread over it.
-  g.stagger = 0; g.stagger_from = 0;
-  if (ntiles > 2 * grid && ntiles % grid) {
-    const int64_t tile_clk = (int64_t)g.NS * 2 * 48 * 32 * 2;
-    g.stagger_from = (int)(ntiles % grid);
-    g.stagger = (int)(tile_clk / (grid - g.stagger_from));
-  }
-  using G3 = cl::Geo<3>;
-  static PerDeviceOnce attr_set;
-  if (const int e = set_max_dyn_lds(attr_set, cl::conv_cl_kernel<3>, G3::SMEM)) return e;
-  cl::conv_cl_kernel<3><<<dim3((unsigned)grid), cl::NT, G3::SMEM, (hipStream_t)stream>>>(g);
-  CPLXAMD_CHECK_LAUNCH();
-  return 0;
+  return cl_launch<true>({x_r, x_i}, w_packed, {bias_r, bias_i}, {y_r, y_i}, B, H, W, C, N, KH, KW, dil_h, dil_w, pad_h, pad_w,
+                         mode, ws, ws_bytes, flags, stream);
+}
+
+// The real-valued cplxamd_conv2d_cl: same arguments (one plane each), same conditions.
+int cplxamd_conv2d_clr(const void* x, const void* w_packed, const float* bias, void* y, int64_t B, int H, int W, int C,
+                       int N, int KH, int KW, int dil_h, int dil_w, int pad_h, int pad_w, int mode, void* ws,
+                       int64_t ws_bytes, void* stream) {
+  return cplxamd_conv2d_clr_fl(x, w_packed, bias, y, B, H, W, C, N, KH, KW, dil_h, dil_w, pad_h, pad_w, mode, ws, ws_bytes,
+                               CPLXAMD_LAUNCH_DEFAULT, stream);
+}
+
+int cplxamd_conv2d_clr_fl(const void* x, const void* w_packed, const float* bias, void* y, int64_t B, int H, int W, int C,
+                          int N, int KH, int KW, int dil_h, int dil_w, int pad_h, int pad_w, int mode, void* ws,
+                          int64_t ws_bytes, int flags, void* stream) {
+  return cl_launch<false>({x, nullptr}, w_packed, {bias, nullptr}, {y, nullptr}, B, H, W, C, N, KH, KW, dil_h, dil_w, pad_h,
+                          pad_w, mode, ws, ws_bytes, flags, stream);
 }
 
 }  // extern "C"

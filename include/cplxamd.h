@@ -712,7 +712,7 @@ int cplxamd_conv2d_cl2_mom_fl(const void* x_r, const void* x_i, const void* w_pa
 int cplxamd_conv2d_cl_wgrad_fl(const void* g_r, const void* g_i, const void* x_r, const void* x_i, const float* emul,
                                float* dw_r, float* dw_i, int64_t B, int H, int W, int Ci, int Co, int KH, int KW, int dil_h,
                                int dil_w, int pad_h, int pad_w, void* ws, int64_t ws_bytes, int flags, void* stream);
-/* REAL-valued twins of the three entry points above (csrc/conv_cl_real.hip, conv_cl_wgrad_real.hip): one plane each,
+/* REAL-valued forms of the three entry points above (the CPLX = false kernels of csrc/conv_cl.hip and conv_cl_wgrad.hip): one plane each,
  * same shapes and conditions.  They carry the variance path of the local-reparameterization convolution layers
  * (conv of |x|^2 with exp(log_sigma2): nn/relevance/complex/base.py:120-135, real/base.py:116-163) and the real
  * Conv2dVD / ARD layers; cplxamd_conv2d_clr_wgrad can multiply the result by emul or exp(emul) ([Co][Ci][3][3] float32:

@@ -403,7 +403,7 @@ def _seams(c, which, idx, shape):
         out.append("image border")
     route = c["dgrad"] if which.startswith("dx") else c["fwd"]
     p = (b * H + h) * W + w
-    pg = (b * c["H"] + h) * c["W"] + w       # conv_cl / conv_cl_real walk the LARGER image's grid (the convolution's input)
+    pg = (b * c["H"] + h) * c["W"] + w       # conv_cl.hip, complex and real, walks the LARGER image's grid (the convolution's input)
     if route in ("cl2", "x2"):
         if h % CL2_TH in (0, CL2_TH - 1) or w % CL2_TW in (0, CL2_TW - 1):
             out.append(f"tile border (16 x 32 tile {h // CL2_TH},{w // CL2_TW})")

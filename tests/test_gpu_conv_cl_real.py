@@ -1,4 +1,4 @@
-"""Real-valued channels-last conv kernels (csrc/conv_cl_real.hip, conv_cl_wgrad_real.hip) and the local-
+"""Real-valued channels-last conv kernels (the CPLX = false kernels of csrc/conv_cl.hip and conv_cl_wgrad.hip) and the local-
 reparameterization conv layers that run on them + the complex ones end to end (mean conv, variance conv, noise
 injection, all gradients) against the float64 numpy oracle on the bf16-rounded operands, with a supplied noise tape."""
 import numpy as np
