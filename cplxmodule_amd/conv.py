@@ -782,8 +782,12 @@ def _x2_conv_wgrad(gp, xp, geom, w_shape):
         dwr[:Co, :Ci] = 0
         dwi[:Co, :Ci] = 0
         tot_r, tot_i = (dwr, dwi) if tot_r is None else (tot_r + dwr, tot_i + dwi)
-    alpha = gp[0].scale[1] * xp[0].scale[1]
-    pick = lambda t: ((t[Co:, :Ci] + t[:Co, Ci:]) + t[Co:, Ci:]) * alpha  # noqa: E731  (g0 x1) + (g1 x0) + (g0 x0)
+    # the scale undo in two factors: 1 / (sg sx) itself leaves float32's range when both operands are tiny (or both huge);
+    # same rule as the kernels' (csrc/common.h scale_undo) -- one exact product when the factors lie on opposite sides of 1
+    ig, ix = gp[0].scale[1], xp[0].scale[1]
+    mixed = (ig > 1) != (ix > 1)
+    a1, a2 = torch.where(mixed, ig * ix, ig), torch.where(mixed, torch.ones_like(ix), ix)
+    pick = lambda t: ((t[Co:, :Ci] + t[:Co, Ci:]) + t[Co:, Ci:]) * a1 * a2  # noqa: E731  (g0 x1) + (g1 x0) + (g0 x0)
     return pick(tot_r).reshape(w_shape).contiguous(), pick(tot_i).reshape(w_shape).contiguous()
 
 

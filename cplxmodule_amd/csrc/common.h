@@ -246,6 +246,27 @@ __device__ __forceinline__ float u01(uint32_t x) {
   return fmaf((float)(x >> 8), 5.9604644775390625e-08f, 2.98023223876953125e-08f);
 }
 
+// Scale undo of the half-precision split products (split.hip, 'x2'): the operands carry powers of two sa, sb with
+// exponents in [-120, 120]; scale_a / scale_b = device {s, 1 / s}.  The accumulators hold sa sb C, and sa sb itself
+// leaves float32's range when both operands are tiny (max|A| max|B| <= 2^-98: sa sb = inf, 1 / (sa sb) = 0) or both huge.
+// So the undo is two multiplies, acc * a1 * a2, whose intermediate stays finite and normal whenever the result does:
+//   1/sa and 1/sb on the same side of 1: a1 = 1/sa, a2 = 1/sb (the intermediate lies between acc and the result);
+//   on opposite sides: a1 = (1/sa)(1/sb), exact and within 2^+-120, a2 = 1.
+// Either way the same bits as acc * (1/sa 1/sb) wherever that product was representable.  A bias cannot ride in scaled
+// accumulators (it would start as bias * (sa sb), which is inf for tiny operands and made a zero bias NaN): the scaled
+// kernels add it behind the undo, whatever the scales -- one order of operations, so that C(A 2^p, B 2^q, bias 2^(p+q))
+// is C(A, B, bias) 2^(p+q) bit for bit while the exponents stay inside the clip.
+struct ScaleUndo { float a1, a2; };
+__device__ __forceinline__ ScaleUndo scale_undo(const float* scale_a, const float* scale_b) {
+  ScaleUndo u{1.0f, 1.0f};
+  if (!scale_a) return u;
+  const float ia = scale_a[1], ib = scale_b[1];
+  const bool mixed = (ia > 1.0f) != (ib > 1.0f);
+  u.a1 = mixed ? ia * ib : ia;
+  u.a2 = mixed ? 1.0f : ib;
+  return u;
+}
+
 // grid for HBM-bound streaming kernels: cap at 256 CUs x 8 blocks, grid-stride the rest
 inline int stream_grid(int64_t work_items, int block) {
   int64_t g = (work_items + block - 1) / block;

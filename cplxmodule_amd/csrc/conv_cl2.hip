@@ -417,7 +417,8 @@ __global__ __launch_bounds__(NT) void conv_cl2_kernel(Args g) {
   auto epilogue_f32 = [&]() __attribute__((always_inline)) {
     const int t = opaque_tid();
     const int ln = t & 63, w_ = t >> 6, q31 = ln & 31, qk = ln >> 5;
-    const float alpha = g.scale_a ? g.scale_a[1] * g.scale_b[1] : 1.0f;
+    const ScaleUndo undo = scale_undo(g.scale_a, g.scale_b);       // two factors: 1 / (sa sb) itself may leave float32's range
+    const bool late_bias = g.bias_r && g.scale_a;                  // (init_acc left the bias out)
     const int64_t ldc = g.Cout;
     const int x = tc.x0 + q31;
 #pragma unroll
@@ -434,7 +435,12 @@ __global__ __launch_bounds__(NT) void conv_cl2_kernel(Args g) {
             for (int q = 0; q < 4; ++q) {
               f4 v;
 #pragma unroll
-              for (int e = 0; e < 4; ++e) v.v[e] = (pl ? acc_i[i][j][4 * q + e] : acc_r[i][j][4 * q + e]) * alpha;
+              for (int e = 0; e < 4; ++e) v.v[e] = (pl ? acc_i[i][j][4 * q + e] : acc_r[i][j][4 * q + e]) * undo.a1 * undo.a2;
+              if (late_bias) {
+                const f4 b = ld4((pl ? g.bias_i : g.bias_r) + tc.nt * BN + 4 * qk + j * 32 + 8 * q);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v.v[e] += b.v[e];
+              }
               float* dst = out + j * 32 + 8 * q;
               if (g.accumulate) {
                 const f4 o = ld4(dst);
@@ -587,12 +593,8 @@ __global__ __launch_bounds__(NT) void conv_cl2_kernel(Args g) {
         for (int q = 0; q < 4; ++q) {
           f4 b = {{0.f, 0.f, 0.f, 0.f}};
           if (g.bias_r) b = ld4(reinterpret_cast<const float*>(breg + pl * 256 + (j * 32 + 8 * q + 4 * qk) * 4));
-#ifdef CPLXAMD_CONV_F16     // (the accumulators are multiplied by 1 / (sa sb) in the epilogue: the bias starts as bias sa sb)
-          if (g.bias_r && g.scale_a) {
-            const float inv = g.scale_a[0] * g.scale_b[0];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) b.v[e] *= inv;
-          }
+#ifdef CPLXAMD_CONV_F16     // (scaled accumulators carry no bias: the epilogue adds it behind the scale undo, common.h scale_undo)
+          if (g.scale_a) b = f4{{0.f, 0.f, 0.f, 0.f}};
 #endif
 #pragma unroll
           for (int i = 0; i < 2; ++i)

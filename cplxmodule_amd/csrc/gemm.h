@@ -33,8 +33,9 @@ struct GemmArgs {
   const void* fx_r = nullptr; const void* fx_i = nullptr; const void* fga = nullptr; int64_t fld = 0;
   // operand scales of the half-precision split products (x3.py 'x2' mode, csrc/split.hip): the operands were multiplied by
   // powers of two sa, sb before they were cut into fp16 pieces; scale_a / scale_b point at DEVICE float[2] = {s, 1 / s}.
-  // The accumulators are multiplied by 1 / (sa sb) right behind the K loop (exact: powers of two), a bias that rides in
-  // the accumulators starts as bias * (sa sb).  nullptr (both): no scaling.
+  // The accumulators are multiplied by 1 / (sa sb) right behind the K loop, in two factors neither of which leaves
+  // float32's range (exact: powers of two; common.h scale_undo); the bias does not ride in scaled accumulators (it
+  // would start as bias * (sa sb), inf for tiny operands): it is added behind the undo.  nullptr (both): no scaling.
   const float* scale_a = nullptr; const float* scale_b = nullptr;
   // per-call launch policy (host side only; include/cplxamd.h CPLXAMD_LAUNCH_*, launch.h)
   int flags = 0;
@@ -44,9 +45,8 @@ struct GemmArgs {
 };
 
 __device__ __forceinline__ float gemm_beta(const GemmArgs& g) { return (g.accumulate && g.beta) ? *g.beta : 1.0f; }
-// 1 / (sa sb) and sa sb of the scaled split products (1, 1 without scales)
-__device__ __forceinline__ float gemm_alpha(const GemmArgs& g) { return g.scale_a ? g.scale_a[1] * g.scale_b[1] : 1.0f; }
-__device__ __forceinline__ float gemm_alpha_inv(const GemmArgs& g) { return g.scale_a ? g.scale_a[0] * g.scale_b[0] : 1.0f; }
+// the scale undo of the scaled split products as two factors (common.h)
+__device__ __forceinline__ ScaleUndo gemm_scale_undo(const GemmArgs& g) { return scale_undo(g.scale_a, g.scale_b); }
 
 // (CPLXAMD_MFMA16, the 16-bit matrix instruction of this translation unit: common.h)
 __device__ __forceinline__ float gemm_emul(const GemmArgs& g, float m) { return g.emul_exp ? expf(m) : m; }

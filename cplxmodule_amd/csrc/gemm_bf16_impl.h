@@ -169,7 +169,13 @@ __global__ __launch_bounds__((Cfg<CPLX>::NT), 2) void gemm_bf16_kernel(GemmArgs 
   // ahead of the prologue's LDS-DMA, and land while the first K tiles are fetched.  In the epilogue the same
   // values cost 128 dependent 4-byte loads per wave with nothing to overlap (18 us of the 52 us the bf16
   // forward epilogue took, profiles/r02_gemm_ablation.md).
+#ifdef CPLXAMD_GEMM_F16    // (the half-operand build only: the bf16 kernels' code is untouched)
+  // scaled split products (gemm.h): the bias takes the epilogue's own bias path, behind the scale undo
+  const ScaleUndo undo = gemm_scale_undo(g);
+  const bool bias_in_acc = g.bias_r != nullptr && g.g1 == nullptr && g.splits <= 1 && g.scale_a == nullptr;
+#else
   const bool bias_in_acc = g.bias_r != nullptr && g.g1 == nullptr && g.splits <= 1;
+#endif
   f4 bias_v[CPLX ? 2 : 1][JB][4];
   if (bias_in_acc) {
     const bool vec = (g.N & 3) == 0 && (reinterpret_cast<uintptr_t>(g.bias_r) & 15) == 0 &&
@@ -190,19 +196,6 @@ __global__ __launch_bounds__((Cfg<CPLX>::NT), 2) void gemm_bf16_kernel(GemmArgs 
           }
         }
     }
-#ifdef CPLXAMD_GEMM_F16    // (the half-operand build only: the bf16 kernels' code is untouched)
-    if (g.scale_a) {          // scaled split products (gemm.h): the accumulators are multiplied by 1 / (sa sb) behind the K loop
-      const float inv = gemm_alpha_inv(g);
-#pragma unroll
-      for (int pl = 0; pl < (CPLX ? 2 : 1); ++pl)
-#pragma unroll
-        for (int j = 0; j < JB; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bias_v[pl][j][q].v[e] *= inv;
-    }
-#endif
   }
   auto apply_bias = [&]() __attribute__((always_inline)) {
     if (!bias_in_acc) return;
@@ -422,13 +415,12 @@ __global__ __launch_bounds__((Cfg<CPLX>::NT), 2) void gemm_bf16_kernel(GemmArgs 
 
 #ifdef CPLXAMD_GEMM_F16
   if (g.scale_a) {              // scaled split products (gemm.h): exact, the scales are powers of two
-    const float alpha = gemm_alpha(g);
 #pragma unroll
     for (int i = 0; i < IB; ++i)
 #pragma unroll
       for (int j = 0; j < JB; ++j) {
-        acc_r[i][j] *= alpha;
-        if (CPLX) acc_i[i][j] *= alpha;
+        acc_r[i][j] = acc_r[i][j] * undo.a1 * undo.a2;
+        if (CPLX) acc_i[i][j] = acc_i[i][j] * undo.a1 * undo.a2;
       }
   }
 #endif

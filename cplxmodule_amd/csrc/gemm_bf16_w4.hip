@@ -220,7 +220,13 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
   f32x16 acc_r[IB][JB], acc_i[CPLX ? IB : 1][JB];
 
   // bias rides in the accumulators (see gemm_bf16_kernel)
+#ifdef CPLXAMD_GEMM_F16    // (the half-operand build only: the bf16 kernels' code is untouched)
+  // scaled split products (gemm.h): the bias stays out of the accumulators and is added behind the scale undo
+  const ScaleUndo undo = gemm_scale_undo(g);
+  const bool has_bias = g.bias_r != nullptr && g.scale_a == nullptr;
+#else
   const bool has_bias = g.bias_r != nullptr;
+#endif
   f4 bias_v[NPL][JB][4];
   if (has_bias) {
 #pragma unroll
@@ -231,19 +237,6 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
 #pragma unroll
         for (int q = 0; q < 4; ++q) bias_v[pl][j][q] = ld4(bias + n0 + wn + j * 32 + 8 * q + 4 * lk);
     }
-#ifdef CPLXAMD_GEMM_F16    // (the half-operand build only: the bf16 kernels' code is untouched)
-    if (g.scale_a) {          // scaled split products: the accumulators are multiplied by 1 / (sa sb) behind the K loop
-      const float inv = gemm_alpha_inv(g);
-#pragma unroll
-      for (int pl = 0; pl < NPL; ++pl)
-#pragma unroll
-        for (int j = 0; j < JB; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bias_v[pl][j][q].v[e] *= inv;
-    }
-#endif
   }
 
   // ---- staging registers: [parity of the K tile][piece] ------------------------------------------------------
@@ -537,14 +530,32 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, const int lin0, char*
 #ifdef CPLXAMD_GEMM_F16
   if constexpr (!PERSIST) {
     if (g.scale_a) {            // scaled split products (gemm.h): exact, the scales are powers of two
-      const float alpha = gemm_alpha(g);
 #pragma unroll
       for (int i = 0; i < IB; ++i)
 #pragma unroll
         for (int j = 0; j < JB; ++j) {
-          acc_r[i][j] *= alpha;
-          if (CPLX) acc_i[i][j] *= alpha;
+          acc_r[i][j] = acc_r[i][j] * undo.a1 * undo.a2;
+          if (CPLX) acc_i[i][j] = acc_i[i][j] * undo.a1 * undo.a2;
         }
+      if (g.bias_r != nullptr) {                  // the bias, which cannot ride in scaled accumulators (whole tiles: no bounds)
+#pragma unroll
+        for (int pl = 0; pl < NPL; ++pl) {
+          const float* bias = pl ? g.bias_i : g.bias_r;
+#pragma unroll
+          for (int j = 0; j < JB; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const f4 b = ld4(bias + n0 + wn + j * 32 + 8 * q + 4 * lk);
+#pragma unroll
+              for (int i = 0; i < IB; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                  if (pl) acc_i[CPLX ? i : 0][j][4 * q + e] += b.v[e];
+                  else acc_r[i][j][4 * q + e] += b.v[e];
+                }
+            }
+        }
+      }
     }
   }
 #endif

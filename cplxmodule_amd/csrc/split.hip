@@ -88,6 +88,14 @@ static int launch_split3(const float* src, const float* src2, int64_t ld_src, bf
 // an element keeps all 22 bits while |x| >= 2^-17 max|x|, below that its second piece goes subnormal (absolute error
 // <= 2^-25 in scaled units = 2^-39 max|x|).  Three piece products (h0 w0, h0 w1, h1 w0) instead of bf16's six.
 // Pieces: pattern A (h1, h0); pattern B (w1, w0, w0):   launch 1: h0 . w1    launch 2: [h1|h0] . [w0|w0].
+// Element by element that is  dx = max(2^-22 |x s|, 2^-25) / s  with ONE s per tensor, and a product C = A B^T obeys
+//     |C - A B^T|[m, n] <= sum_k (da |b| + |a| db + da db) + gamma(3 K) sum_k |a| |b|      (gamma(n) = n 2^-24 / (1 - n 2^-24))
+// (bf16 pieces: da = 2^-24 |a|, no scale).  An element below 2^-17 max|x| keeps 11 bits, one below 2^-41 max|x| is 0: a
+// whole ROW that small -- a sample far below the batch's largest, squared by OP_ABS2; an output unit's variances under
+// OP_EXP -- comes back wrong at 2^-11 or as zeros while the tensor's norm-wise error stays at 2^-22.  That is why the
+// 'auto' mode runs the products with an OP_ABS2 / OP_EXP operand on the bf16 pieces (x3.py variance_kind), and what
+// tests/x2_range_cases.py emulates and bounds.  The exponent of s is clipped to +-120; the GEMMs undo sa sb in two
+// factors, because the product itself leaves float32's range for tiny (or huge) operands (common.h scale_undo).
 
 // stage 1 of max |op(x)|: per-block maxima (NaN / inf propagate as inf: the final stage then falls back to scale 1)
 template <int OP>

@@ -724,15 +724,18 @@ def _real_linear_fwd(x2, w, bias, out_dtype=None, mode=None, xs=None):
     return rgemm(x2, (I, 1), wm, (I, 1), B, O, I, bias=bias, out_dtype=out_dtype or x2.dtype), wm
 
 
-def _real_linear_dx(g2, w, out_dtype, mode=None, gs=None, w_exp=False):
+def _real_linear_dx(g2, w, out_dtype, mode=None, gs=None, w_exp=False, variance=False):
     """G W -> [B, I].  `w_exp` (float32 split products only): the weight operand is exp(w) -- the variance path's
-    sigma^2 = exp(log_sigma2), formed inside the split pass."""
+    sigma^2 = exp(log_sigma2), formed inside the split pass.  `variance`: a product of the variance path
+    (x3.variance_kind: 'auto' runs it on bf16 pieces)."""
     B, O = g2.shape
     I = w.shape[1]
     if _is_bf16(g2):
         w = cast(w, torch.bfloat16)
     elif out_dtype == torch.float32 and x3.take(B, I, O, g2, w, mode=mode):
         kind = x3.take(B, I, O, mode=mode)
+        if variance or w_exp:
+            kind = x3.variance_kind(kind, mode)
         Wst = x3.split(w, x3.SPLIT_B, op=x3.OP_EXP if w_exp else x3.OP_ID, stacked=True, kind=kind)
         return x3.gemm_nt((gs or _Pieces(g2)).get(kind), (Wst,), B, I, O)
     if w_exp:
@@ -740,12 +743,16 @@ def _real_linear_dx(g2, w, out_dtype, mode=None, gs=None, w_exp=False):
     return rgemm(g2, (O, 1), w, (1, I), B, I, O, out_dtype=out_dtype)
 
 
-def _real_linear_dw(g2, x2, emul=None, out=None, emul_exp=False, accumulate=False, beta=None, mode=None, gs=None, xs=None):
+def _real_linear_dw(g2, x2, emul=None, out=None, emul_exp=False, accumulate=False, beta=None, mode=None, gs=None, xs=None,
+                    variance=False):
     """G^T X (* emul) -> float32 [O, I].  x2 may be None when `xs` (pieces of it, e.g. of |x|^2) is given and the
-    split products take the shape (the caller checked with x3.take)."""
+    split products take the shape (the caller checked with x3.take).  `variance`: a product of the variance path
+    (x3.variance_kind: 'auto' runs it on bf16 pieces)."""
     B, O = g2.shape
     I = x2.shape[1] if x2 is not None else xs.planes[0].shape[1]
     kind = x3.take(O, I, B, g2, x2, mode=mode) if g2.dtype == torch.float32 else None
+    if variance:
+        kind = x3.variance_kind(kind, mode)
     if kind:
         return x3.gemm_tt((gs or _Pieces(g2)).get(kind), (xs or _Pieces(x2)).get(kind), O, I, B, out=out,
                           accumulate=accumulate, beta=beta, emul=emul, emul_exp=emul_exp)
@@ -964,15 +971,17 @@ class CplxLinearLRTFn(torch.autograd.Function):
                      1.0, ptr(kl), ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(_ws(x2r.device)), O * I, stream_ptr())
         ctx.wc, ctx.S = (wcr, wci), S
         keep = (None,) * 5
-        ctx.kind = None
+        ctx.kind = ctx.vkind = None
         if use3:
             xs, xa = _Pieces(x2r, x2i), _Pieces(x2r, x2i, abs2=True)
             mur, mui, _ = _cplx_linear_fwd(x2r, x2i, wcr, wci, bias, mode=mode, xs=xs)
             a = None                                         # |x|^2 exists as 16-bit pieces only
-            s2 = x3.gemm_nn(xa.get(use3), (x3.split(ls2c, x3.SPLIT_B, op=x3.OP_EXP, kind=use3),), B, O, I)
+            vk = x3.variance_kind(use3, mode)                # the variance products' arithmetic ('auto': bf16 pieces)
+            s2 = x3.gemm_nn(xa.get(vk), (x3.split(ls2c, x3.SPLIT_B, op=x3.OP_EXP, kind=vk),), B, O, I)
             ctx.kind = x3.take(O, I, B, mode=mode)           # the weight gradients' arithmetic (K = batch)
-            if ctx.kind == use3:                # they will read the same pieces
-                keep = (*xs.saved(), *xa.saved())
+            ctx.vkind = x3.variance_kind(ctx.kind, mode)     # ... and the variance weight gradient's
+            # they will read the same pieces -- each set kept only if its own kinds agree (mean and variance may differ)
+            keep = (*(xs.saved() if ctx.kind == use3 else (None,) * 3), *(xa.saved() if ctx.vkind == vk else (None,) * 2))
         else:
             mur, mui = cgemm(x2r, x2i, (I, 1), wcr, wci, (I, 1), B, O, I, bias=bias, out_dtype=x2r.dtype)
             a = abs2(x2r, x2i)                                   # [B,I], activation dtype
@@ -1041,7 +1050,7 @@ class CplxLinearLRTFn(torch.autograd.Function):
         xs = _Pieces(x2r, x2i, made=_Pieces.restored(ctx.kind, (xsr, xsi), xsc))
         if a is None:                                        # the forward ran on pieces of |x|^2
             if x3.take(O, I, B, gs2, mode=m3):
-                xa = _Pieces(x2r, x2i, abs2=True, made=_Pieces.restored(ctx.kind, (xsa,), xac))
+                xa = _Pieces(x2r, x2i, abs2=True, made=_Pieces.restored(ctx.vkind, (xsa,), xac))
             else:
                 a = abs2(x2r, x2i)
         if want_w:
@@ -1060,10 +1069,11 @@ class CplxLinearLRTFn(torch.autograd.Function):
         if need[6]:
             if fused:
                 dls2 = klg[0]
-                _real_linear_dw(gs2, a, emul=ls2c, emul_exp=True, out=dls2, accumulate=True, beta=gkl, mode=m3, gs=g2s, xs=xa)
+                _real_linear_dw(gs2, a, emul=ls2c, emul_exp=True, out=dls2, accumulate=True, beta=gkl, mode=m3, gs=g2s, xs=xa,
+                                variance=True)
             else:
                 dls2 = own(ls2)
-                _real_linear_dw(gs2, a, emul=ls2c, emul_exp=True, out=dls2, mode=m3, gs=g2s, xs=xa)  # (gs2^T a) * exp(ls2)
+                _real_linear_dw(gs2, a, emul=ls2c, emul_exp=True, out=dls2, mode=m3, gs=g2s, xs=xa, variance=True)  # (gs2^T a) * exp(ls2)
                 if klg is not None:
                     dls2.add_(klg[0] * gkl)
         if fused or getattr(ctx, "klg_shared", False):
@@ -1073,7 +1083,7 @@ class CplxLinearLRTFn(torch.autograd.Function):
             if ctx.S is None:                                # gs2 . exp(ls2) -> [B,I], sigma^2 formed in the split pass
                 ga = _real_linear_dx(gs2, ls2c, dt, mode=m3, gs=g2s, w_exp=True)
             else:
-                ga = _real_linear_dx(gs2, ctx.S, dt)
+                ga = _real_linear_dx(gs2, ctx.S, dt, mode=m3, variance=True)
             dxr, dxi = _cplx_lrt_dx(g2r, g2i, ctx.wc[0], ctx.wc[1], x2r, x2i, ga, mode=m3, gs=gs)   # G conj(W) + 2 x ga
             dxr, dxi = dxr.view(*ctx.lead, I), dxi.view(*ctx.lead, I)
         return dxr, dxi, dwr, dwi, dbr, dbi, dls2, None, None, None, None, None
@@ -1183,15 +1193,16 @@ class RealLinearLRTFn(torch.autograd.Function):
                      ptr(kl), ptr(ctx.klg[0]), ptr(ctx.klg[1]), None, ptr(_ws(x2.device)), O * I, stream_ptr())
         ctx.wb, ctx.S = wb, S
         keep = (None,) * 4
-        ctx.kind = None
+        ctx.kind = ctx.vkind = None
         if use3:
             xs, xa = _Pieces(x2), _Pieces(x2, abs2=True)
             mu, _ = _real_linear_fwd(x2, wb, _c(b), mode=mode, xs=xs)
             a = None
-            s2 = x3.gemm_nn(xa.get(use3), (x3.split(ls2c, x3.SPLIT_B, op=x3.OP_EXP, kind=use3),), B, O, I)
+            vk = x3.variance_kind(use3, mode)                # (see CplxLinearLRTFn.forward)
+            s2 = x3.gemm_nn(xa.get(vk), (x3.split(ls2c, x3.SPLIT_B, op=x3.OP_EXP, kind=vk),), B, O, I)
             ctx.kind = x3.take(O, I, B, mode=mode)
-            if ctx.kind == use3:
-                keep = (*xs.saved(), *xa.saved())
+            ctx.vkind = x3.variance_kind(ctx.kind, mode)
+            keep = (*(xs.saved() if ctx.kind == use3 else (None,) * 2), *(xa.saved() if ctx.vkind == vk else (None,) * 2))
         else:
             mu = rgemm(x2, (I, 1), wb, (I, 1), B, O, I, bias=_c(b), out_dtype=x2.dtype)
             a = abs2(x2)
@@ -1242,7 +1253,7 @@ class RealLinearLRTFn(torch.autograd.Function):
         xs = None if xsv is None else _Pieces(x2, made=_Pieces.restored(ctx.kind, (xsv,), xsc))
         if a is None:
             if x3.take(O, I, B, gs2, mode=m3):
-                xa = _Pieces(x2, abs2=True, made=_Pieces.restored(ctx.kind, (xsa,), xac))
+                xa = _Pieces(x2, abs2=True, made=_Pieces.restored(ctx.vkind, (xsa,), xac))
             else:
                 a = abs2(x2)
         if need[1]:
@@ -1257,10 +1268,11 @@ class RealLinearLRTFn(torch.autograd.Function):
         if need[3]:
             if fused:
                 dls2 = klg[0]
-                _real_linear_dw(gs2, a, emul=ls2c, emul_exp=True, out=dls2, accumulate=True, beta=gkl, mode=m3, gs=g2s, xs=xa)
+                _real_linear_dw(gs2, a, emul=ls2c, emul_exp=True, out=dls2, accumulate=True, beta=gkl, mode=m3, gs=g2s, xs=xa,
+                                variance=True)
             else:
                 dls2 = own(ls2)
-                _real_linear_dw(gs2, a, emul=ls2c, emul_exp=True, out=dls2, mode=m3, gs=g2s, xs=xa)
+                _real_linear_dw(gs2, a, emul=ls2c, emul_exp=True, out=dls2, mode=m3, gs=g2s, xs=xa, variance=True)
                 if klg is not None:
                     dls2.add_(klg[0] * gkl)
         if fused or getattr(ctx, "klg_shared", False):
@@ -1270,7 +1282,7 @@ class RealLinearLRTFn(torch.autograd.Function):
             if ctx.S is None:
                 ga = _real_linear_dx(gs2, ls2c, dt, mode=m3, gs=g2s, w_exp=True)
             else:
-                ga = _real_linear_dx(gs2, ctx.S, dt)
+                ga = _real_linear_dx(gs2, ctx.S, dt, mode=m3, variance=True)
             dx = _real_lrt_dx(g2, ctx.wb if _is_bf16(g2) else _c(w), x2, ga, mode=m3, gs=gs)
             dx = dx.view(*ctx.lead, I)
         return dx, dw, db, dls2, None, None, None, None

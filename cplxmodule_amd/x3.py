@@ -8,6 +8,23 @@ float32 MFMA of gfx950 peaks at 157 TFLOP/s, the 16-bit ones at 2.5 PFLOP/s.  Tw
   'x2'  x s = h0 + h1 to 2^-22 in IEEE half after a power-of-two scale s per operand (its largest magnitude into
         [2^14, 2^15)); three piece products, the scales undone in the GEMM: 2^-22 norm-wise at 1/3 of the half rate.
 
+Element-wise, C = A B^T on pieces obeys (tests/x2_range_cases.py derives and checks it)
+
+    |C - A B^T|[m, n] <= sum_k (da |b| + |a| db + da db) + gamma(3 K) sum_k |a| |b|,     gamma(n) = n u / (1 - n u), u = 2^-24,
+    'x2': da = max(2^-22 |a s|, 2^-25) / s  per element, s the ONE scale of the whole operand;   'x3': da = 2^-24 |a|.
+
+So 'x3' is accurate row by row, while under 'x2' an element below 2^-17 max|A| loses its second piece to half's subnormals
+and one below 2^-40 max|A| becomes 0: a row of A that small comes back with 11 bits, or as zeros, and the norm of the whole
+result does not show it.  The mean products of a layer live with that (their operands are activations and weights, and a
+sample 2^17 below the batch's largest is rare); the variance products of the LRT layers do not -- their operands |x|^2 and
+exp(log_sigma2) square / exponentiate the dynamic range.  Hence in 'auto' every product with an |x|^2 or exp(log_sigma2)
+operand (the forward's s2, the backward's dlog_sigma2 and d|x|^2) runs on 'x3' pieces, which carry float32's exponent
+range and need no scale (`variance_kind`); the mean products (y, dW, dX) run AUTO_KIND.  Explicit 'x2' keeps every
+product on half pieces.
+
+The scale undo never forms sa sb or its inverse where that leaves float32's range (both operands around 2^-49 and
+smaller: sa sb >= 2^128): two successive factors, and a bias joins behind the undo then (csrc/common.h scale_undo).
+
 This module holds the host side: which products take which arithmetic, the piece layouts, and the launch sequences over
 the MFMA GEMM kernels (cplxamd_cgemm_fl / cplxamd_rgemm_fl for bf16 pieces, cplxamd_cgemm_sc_fl / cplxamd_rgemm_sc_fl
 for half pieces; float32 output, accumulate from the second launch on):
@@ -92,6 +109,15 @@ def take(M, N, K, *tensors, mode=None):
     if mode == "auto":
         return AUTO_KIND if M * N * K >= AUTO_MIN_WORK else None
     return mode
+
+
+def variance_kind(kind, mode=None):
+    """The arithmetic of a product with an |x|^2 or exp(log_sigma2) operand, given what `take` said for its shape: 'auto'
+    moves it to 'x3' (one scale per tensor would leave the small samples / output units of such an operand with 11 bits or
+    none: module docstring); an explicit mode keeps its kind."""
+    if kind and (mode or get_fp32_mode()) == "auto":
+        return "x3"
+    return kind
 
 
 class Pieces:
