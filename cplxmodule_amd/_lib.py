@@ -194,6 +194,12 @@ SIGNATURES = {
     "cplxamd_expand_axis": [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "cplxamd_compact_weight": [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _I, _I, _P],
     "cplxamd_expand_weight": [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _I, _I, _P],
+    # still ABI 25: the native 3-d implicit-GEMM convolution behind CplxConvTranspose3d (csrc/conv3d.hip; geom = int[19])
+    "cplxamd_conv3d_out_shape": [_P, _P, _P, _P],
+    "cplxamd_conv3d_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _P],
+    "cplxamd_conv3d_dgrad": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "cplxamd_conv3d_wgrad_ws_bytes": [_P],
+    "cplxamd_conv3d_wgrad": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -212,6 +218,7 @@ _RESTYPES = {"cplxamd_absmax_ws_bytes": c_int64, "cplxamd_init_ws_bytes": c_int6
              "cplxamd_conv2d_wgrad_ws_bytes": c_int64, "cplxamd_conv2d_bf16_wgrad_ws_bytes": c_int64, "cplxamd_colsum_ws_bytes": c_int64, "cplxamd_gemm_ws_bytes": c_int64,
              "cplxamd_cgemm3m_ws_bytes": c_int64,
              "cplxamd_live_index_ws_bytes": c_int64,
+             "cplxamd_conv3d_wgrad_ws_bytes": c_int64,
              "cplxamd_conv2d_nhwc_wgrad_ws_bytes": c_int64,
              "cplxamd_conv2d_nhwc_wgrad_f32_ws_bytes": c_int64,
              "cplxamd_conv2d_cl_pack_bytes": c_int64, "cplxamd_conv2d_cl_ws_bytes": c_int64,

@@ -528,6 +528,42 @@ def conv_transpose1d(input, weight, bias=None, stride=1, padding=0, output_paddi
                                       dilation, padding_mode)
 
 
+def conv_transpose3d(input, weight, bias=None, stride=1, padding=0, output_padding=0, groups=1,
+                     dilation=1, padding_mode="zeros"):
+    """Complex 3-d transposed convolution on [B, C, D, H, W], weight [in, out / groups, kd, kh, kw], no conjugation
+    (cplxmodule/cplx.py:1004-1029; the reference's functional default `groups=0` is not kept).  Runs the data-gradient
+    kernel of the native 3-d convolution (csrc/conv3d.hip) as the forward pass; float32 and bfloat16 only, no second
+    derivative."""
+    from .conv3d import cplx_conv_transpose3d
+    return cplx_conv_transpose3d(input, weight, bias, stride, padding, output_padding, groups, dilation, padding_mode)
+
+
+def conv_transposend(conv, input, weight, bias=None, stride=1, padding=0, output_padding=0, groups=1, dilation=1,
+                     padding_mode="zeros"):
+    """The reference's module-level transposed operator (cplxmodule/cplx.py:916-945).  As in `convnd`, `conv` -- there
+    the real torch functional that does the work (F.conv_transpose1d / 2d / 3d) -- only names the dimensionality here
+    (None: decided by input.dim()); the kernels behind conv_transpose1d / 2d / 3d run."""
+    nd = input.dim() - 2
+    name = getattr(conv, "__name__", "") if conv is not None else ""
+    if name in ("conv_transpose1d", "conv_transpose2d", "conv_transpose3d") and int(name[14]) != nd:
+        raise ValueError(f"{name} on a {input.dim()}-d input")
+    fn = {1: conv_transpose1d, 2: conv_transpose2d, 3: conv_transpose3d}.get(nd)
+    if fn is None:
+        raise ValueError(f"conv_transposend: {nd} spatial dimensions are not supported (1, 2 or 3)")
+    return fn(input, weight, bias, stride, padding, output_padding, groups, dilation, padding_mode)
+
+
+def conv_transposend_naive(conv_t, input, weight, stride=1, padding=0, output_padding=0, groups=1, dilation=1):
+    """cplxmodule/cplx.py:860-873 (four real transposed convolutions): the same complex kernels."""
+    return conv_transposend(conv_t, input, weight, None, stride, padding, output_padding, groups, dilation)
+
+
+def conv_transposend_3m(conv_t, input, weight, stride=1, padding=0, output_padding=0, groups=1, dilation=1):
+    """cplxmodule/cplx.py:876-913 (Gauss's three real transposed convolutions): routed to the four-product kernels, like
+    convnd_3m."""
+    return conv_transposend(conv_t, input, weight, None, stride, padding, output_padding, groups, dilation)
+
+
 def from_interleaved_real(input, copy=True, dim=-1):
     """[..., 2D] interleaved (re, im) -> Cplx [..., D]  (cplxmodule/cplx.py:451-455).  copy=True along
     the last dim on the GPU is one de-interleaving kernel pass (csrc/layout.hip) instead of two

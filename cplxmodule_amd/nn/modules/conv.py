@@ -135,7 +135,7 @@ class CplxConvTranspose2d(CplxConv2d):
             raise ValueError("in_channels must be divisible by groups")
         if out_channels % groups != 0:
             raise ValueError("out_channels must be divisible by groups")
-        tup = _pair if self._nd == 2 else _single
+        tup = {1: _single, 2: _pair, 3: _triple}[self._nd]
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride = tup(kernel_size), tup(stride)
         self.padding, self.dilation = tup(padding), tup(dilation)
@@ -179,3 +179,11 @@ class CplxConvTranspose2d(CplxConv2d):
 class CplxConvTranspose1d(CplxConvTranspose2d):
     _nd = 1
     _fn = staticmethod(cplx.conv_transpose1d)
+
+
+class CplxConvTranspose3d(CplxConvTranspose2d):
+    """[B, C, D, H, W] complex transposed convolution; weight [in, out / groups, kd, kh, kw] (conv.py:383-415 of the
+    reference, whose `forward` no longer runs on current torch; `output_size` works here).  Runs the native 3-d kernel
+    (cplx.conv_transpose3d): float32 and bfloat16, no float64 form, no second derivative."""
+    _nd = 3
+    _fn = staticmethod(cplx.conv_transpose3d)

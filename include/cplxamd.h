@@ -733,6 +733,38 @@ int cplxamd_conv2d_clr_fl(const void* x, const void* w_packed, const float* bias
 int cplxamd_conv2d_clr_wgrad_fl(const void* g, const void* x, const float* emul, int emul_exp, float* dw, int64_t B, int H,
                                 int W, int Ci, int Co, int KH, int KW, int dil_h, int dil_w, int pad_h, int pad_w, void* ws,
                                 int64_t ws_bytes, int flags, void* stream);
+/* ------------------------------------------------------------------------------------
+ * K3: complex 3-d convolution as implicit GEMM on the float32 matrix instruction (csrc/conv3d.hip; still ABI 25: exports
+ * added).  The kernel behind cplx.conv_transpose3d / nn.CplxConvTranspose3d, whose forward pass is the data gradient.
+ * Replaces: cplx.conv_transposend / conv_transposend_naive / conv_transpose3d   cplx.py:860-1029
+ * Planar [B, C, D, H, W] operands of element type `dtype` (CPLXAMD_F32 or CPLXAMD_BF16; converted to float32 on load,
+ * float32 sums, one rounding on store).  Complex only: a NULL imaginary plane is CPLXAMD_EINVAL.
+ * geom = int[19] {B, Ci, Co, D, H, W, KD, KH, KW, stride_d, stride_h, stride_w, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w,
+ * groups} describes the forward correlation; weight [Co, Ci/groups, KD, KH, KW].
+ *   fwd   : y = x (*) w                         (no conjugation, no bias)
+ *   dgrad : dx = g (*)^T conj(w) (+ bias)       bias: float32 [Ci] pair (both or neither), added to the float32 sums
+ *           before their one rounding.  Strides of 1 or 2 per dimension (at least one 2) run by stride phases: up to 8
+ *           classes of voxels, each a GEMM over its valid taps only; every voxel of dx is written, also those of a
+ *           class without a valid tap (bias, or zero).  flags: 0, or CPLXAMD_CONV3D_PLAIN = the plain path (every tap
+ *           tested per voxel) at any stride -- the same sums; for measuring what the phases save.  Other bits: EINVAL.
+ *   wgrad : dw = sum g conj(x)   (float32 out); split-K partial slabs live in `ws` (>= cplxamd_conv3d_wgrad_ws_bytes,
+ *           which returns -1 for an invalid geometry) and are summed in a fixed order: no atomics, the same bits on
+ *           every run.  The bias gradient is cplxamd_chansum2 on the output gradient (S = D * H * W).
+ * Voxel and tap indices are 32-bit: a GEMM dimension or voxel count above 0x7fe00000, or a launch grid above 65535 in
+ * y / z, is CPLXAMD_ESHAPE, as is an empty output or channels that the groups do not divide; a non-positive stride,
+ * dilation or groups is CPLXAMD_EINVAL.  All checks precede any launch.  No host synchronisation, no allocation; an empty
+ * batch returns 0 without a launch (wgrad: zero-fills dw).
+ * ---------------------------------------------------------------------------------- */
+#define CPLXAMD_CONV3D_PLAIN 1
+int cplxamd_conv3d_out_shape(const int* geom, int* dout, int* ho, int* wo);
+int cplxamd_conv3d_fwd(const void* xr, const void* xi, const void* wr, const void* wi, void* yr, void* yi,
+                       const int* geom, int dtype, void* stream);
+int cplxamd_conv3d_dgrad(const void* gr, const void* gi, const void* wr, const void* wi, const float* bias_r,
+                         const float* bias_i, void* dxr, void* dxi, const int* geom, int dtype, int flags, void* stream);
+int64_t cplxamd_conv3d_wgrad_ws_bytes(const int* geom);
+int cplxamd_conv3d_wgrad(const void* gr, const void* gi, const void* xr, const void* xi, float* dwr, float* dwi,
+                         const int* geom, int dtype, void* ws, int64_t ws_bytes, void* stream);
+
 /* out[c] = sum over (batch, spatial) of an NCHW tensor (conv bias gradient); ws >= 64*C*8 bytes */
 int cplxamd_chansum(const void* x, float* out, int64_t B, int C, int64_t S, int dtype, void* ws,
                     void* stream);
