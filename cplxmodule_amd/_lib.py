@@ -182,6 +182,8 @@ SIGNATURES = {
     "cplxamd_welch_bwd": [_P, _P, _L, _L, _L, _L, _P, _L, _L, _I, _D, _P, _P, _P, _L, _L, _P, _L, _I, _P],
     # still ABI 25: the strided complex contraction behind cplx.einsum (the descriptor is a host struct, EinsumDesc)
     "cplxamd_ceinsum": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    # still ABI 25: its dispatch as a pure function (addresses as integers, plan = int64[5]: ops.einsum_dispatch)
+    "cplxamd_einsum_plan": [_P, _U, _U, _U, _U, _I, _P],
     # still ABI 25: the finishing kernels of the semi-unitary initialiser (nn/init.py; F64 is a plane dtype here)
     "cplxamd_init_ws_bytes": [],
     "cplxamd_init_moments": [_P, _P, _L, _I, _P, _P, _P],

@@ -37,7 +37,8 @@
 namespace cplxamd {
 
 
-enum { ELOAD_KFAST = 0, ELOAD_KVEC = 1, ELOAD_ROWS = 2, ELOAD_ROWVEC = 3 };
+enum { ELOAD_KFAST = CPLXAMD_EINSUM_LOAD_KFAST, ELOAD_KVEC = CPLXAMD_EINSUM_LOAD_KVEC, ELOAD_ROWS = CPLXAMD_EINSUM_LOAD_ROWS,
+       ELOAD_ROWVEC = CPLXAMD_EINSUM_LOAD_ROWVEC };
 constexpr int EG_B = CPLXAMD_EINSUM_BATCH, EG_M = CPLXAMD_EINSUM_M, EG_N = CPLXAMD_EINSUM_N, EG_K = CPLXAMD_EINSUM_K;
 constexpr int EMAX = CPLXAMD_EINSUM_MAX_MODES;
 
@@ -499,32 +500,22 @@ static int einsum_load_mode(const cplxamd_einsum_desc& d, const int64_t (*st)[EM
   return ELOAD_KFAST;
 }
 
-static int launch_einsum(EinsumArgs& g, int dtype, hipStream_t st) {
-  // 128 x 128 tiles when they fill the chip, else 64 x 64 (a function of the extents alone)
+// 128 x 128 tiles when they fill the chip, else 64 x 64 (a function of the extents alone)
+static int einsum_tile(const EinsumArgs& g) {
   const int64_t big = (int64_t)g.B * ((g.M + 127) / 128) * ((g.N + 127) / 128);
-  const int bm = (g.M > 64 || g.N > 64) && big >= 256 ? 128 : 64;
-  g.tiles_m = (g.M + bm - 1) / bm;
-  g.tiles_n = (g.N + bm - 1) / bm;
-  const int64_t grid = (int64_t)g.B * g.tiles_m * g.tiles_n;
-  if (grid > INT_MAX) return CPLXAMD_ESHAPE;
-  if (dtype == CPLXAMD_F32) {
-    if (bm == 128) einsum_f32_kernel<2><<<dim3((uint32_t)grid), 256, 0, st>>>(g);
-    else einsum_f32_kernel<1><<<dim3((uint32_t)grid), 256, 0, st>>>(g);
-  } else {
-    if (bm == 128) einsum_bf16_kernel<2><<<dim3((uint32_t)grid), 256, 0, st>>>(g);
-    else einsum_bf16_kernel<1><<<dim3((uint32_t)grid), 256, 0, st>>>(g);
-  }
-  CPLXAMD_CHECK_LAUNCH();
-  return 0;
+  return (g.M > 64 || g.N > 64) && big >= 256 ? 128 : 64;
 }
 
-}  // namespace cplxamd
+struct EinsumDispatch {
+  int swapped, tile;
+  int64_t grid;     // 0: an empty result, nothing to launch
+};
 
-extern "C" int cplxamd_ceinsum(const void* a_r, const void* a_i, const void* b_r, const void* b_i, void* c_r, void* c_i,
-                               const cplxamd_einsum_desc* d, int conj_a, int conj_b, int in_dtype, int out_dtype,
-                               void* stream) {
-  using namespace cplxamd;
-  if (!a_r || !a_i || !b_r || !b_i || !c_r || !c_i || !d) return CPLXAMD_EINVAL;
+// Every host-side decision of a contraction: argument checks, the M / N swap, the load mode of both operands, the tile and
+// the grid.  Only the low four bits of the operand addresses are looked at; no GPU call.
+static int einsum_dispatch(EinsumArgs& g, EinsumDispatch& dp, const void* a_r, const void* a_i, const void* b_r, const void* b_i,
+                           const cplxamd_einsum_desc* d, int conj_a, int conj_b, int in_dtype, int out_dtype) {
+  if (!d) return CPLXAMD_EINVAL;
   for (int grp = 0; grp < 4; ++grp) {
     if (d->nmodes[grp] < 0 || d->nmodes[grp] > EMAX) return CPLXAMD_EINVAL;
     for (int i = 0; i < d->nmodes[grp]; ++i) {
@@ -533,14 +524,16 @@ extern "C" int cplxamd_ceinsum(const void* a_r, const void* a_i, const void* b_r
     }
   }
   if ((in_dtype != CPLXAMD_F32 && in_dtype != CPLXAMD_BF16) || out_dtype != in_dtype) return CPLXAMD_ESHAPE;
-  EinsumArgs g;
   g.d = *d;
   if (!einsum_group_total(g.d, EG_B, &g.B) || !einsum_group_total(g.d, EG_M, &g.M) ||
       !einsum_group_total(g.d, EG_N, &g.N) || !einsum_group_total(g.d, EG_K, &g.K))
     return CPLXAMD_ESHAPE;
-  if (g.B == 0 || g.M == 0 || g.N == 0) return 0;
-  g.a_r = a_r; g.a_i = a_i; g.b_r = b_r; g.b_i = b_i; g.c_r = c_r; g.c_i = c_i;
+  g.a_r = a_r; g.a_i = a_i; g.b_r = b_r; g.b_i = b_i;
   g.conj_a = conj_a != 0; g.conj_b = conj_b != 0;
+  g.mode_a = g.mode_b = ELOAD_KFAST;
+  g.tiles_m = g.tiles_n = 0;
+  dp.swapped = 0; dp.tile = 64; dp.grid = 0;
+  if (g.B == 0 || g.M == 0 || g.N == 0) return 0;
   // the store runs along N: when C's unit stride is in an M mode, compute C^T = B A^T instead
   const int nm = g.d.nmodes[EG_M], nn = g.d.nmodes[EG_N];
   const bool n_unit = nn > 0 && g.d.stride_c[EG_N][nn - 1] == 1, m_unit = nm > 0 && g.d.stride_c[EG_M][nm - 1] == 1;
@@ -562,9 +555,59 @@ extern "C" int cplxamd_ceinsum(const void* a_r, const void* a_i, const void* b_r
     g.a_r = b_r; g.a_i = b_i; g.b_r = a_r; g.b_i = a_i;
     g.conj_a = conj_b != 0; g.conj_b = conj_a != 0;
     const uint32_t tmp = g.M; g.M = g.N; g.N = tmp;
+    dp.swapped = 1;
   }
   const int esize = in_dtype == CPLXAMD_F32 ? 4 : 2;
   g.mode_a = einsum_load_mode(g.d, g.d.stride_a, EG_M, g.a_r, g.a_i, esize);
   g.mode_b = einsum_load_mode(g.d, g.d.stride_b, EG_N, g.b_r, g.b_i, esize);
-  return launch_einsum(g, in_dtype, (hipStream_t)stream);
+  dp.tile = einsum_tile(g);
+  g.tiles_m = (g.M + dp.tile - 1) / dp.tile;
+  g.tiles_n = (g.N + dp.tile - 1) / dp.tile;
+  dp.grid = (int64_t)g.B * g.tiles_m * g.tiles_n;
+  if (dp.grid > INT_MAX) return CPLXAMD_ESHAPE;
+  return 0;
+}
+
+static int launch_einsum(const EinsumArgs& g, const EinsumDispatch& dp, int dtype, hipStream_t st) {
+  if (dtype == CPLXAMD_F32) {
+    if (dp.tile == 128) einsum_f32_kernel<2><<<dim3((uint32_t)dp.grid), 256, 0, st>>>(g);
+    else einsum_f32_kernel<1><<<dim3((uint32_t)dp.grid), 256, 0, st>>>(g);
+  } else {
+    if (dp.tile == 128) einsum_bf16_kernel<2><<<dim3((uint32_t)dp.grid), 256, 0, st>>>(g);
+    else einsum_bf16_kernel<1><<<dim3((uint32_t)dp.grid), 256, 0, st>>>(g);
+  }
+  CPLXAMD_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace cplxamd
+
+extern "C" int cplxamd_ceinsum(const void* a_r, const void* a_i, const void* b_r, const void* b_i, void* c_r, void* c_i,
+                               const cplxamd_einsum_desc* d, int conj_a, int conj_b, int in_dtype, int out_dtype,
+                               void* stream) {
+  using namespace cplxamd;
+  if (!a_r || !a_i || !b_r || !b_i || !c_r || !c_i || !d) return CPLXAMD_EINVAL;
+  EinsumArgs g;
+  EinsumDispatch dp;
+  const int rc = einsum_dispatch(g, dp, a_r, a_i, b_r, b_i, d, conj_a, conj_b, in_dtype, out_dtype);
+  if (rc != 0 || dp.grid == 0) return rc;
+  g.c_r = c_r; g.c_i = c_i;
+  return launch_einsum(g, dp, in_dtype, (hipStream_t)stream);
+}
+
+extern "C" int cplxamd_einsum_plan(const cplxamd_einsum_desc* d, uint64_t a_r, uint64_t a_i, uint64_t b_r, uint64_t b_i,
+                                   int dtype, int64_t* plan) {
+  using namespace cplxamd;
+  if (!d || !plan) return CPLXAMD_EINVAL;
+  EinsumArgs g;
+  EinsumDispatch dp;
+  const int rc = einsum_dispatch(g, dp, (const void*)(uintptr_t)a_r, (const void*)(uintptr_t)a_i, (const void*)(uintptr_t)b_r,
+                                 (const void*)(uintptr_t)b_i, d, 0, 0, dtype, dtype);
+  if (rc != 0) return rc;
+  plan[CPLXAMD_EINSUM_PLAN_MODE_A] = g.mode_a;
+  plan[CPLXAMD_EINSUM_PLAN_MODE_B] = g.mode_b;
+  plan[CPLXAMD_EINSUM_PLAN_SWAPPED] = dp.swapped;
+  plan[CPLXAMD_EINSUM_PLAN_TILE] = dp.tile;
+  plan[CPLXAMD_EINSUM_PLAN_GRID] = dp.grid;
+  return 0;
 }

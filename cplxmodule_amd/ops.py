@@ -332,6 +332,19 @@ def einsum_desc(plan):
     return d
 
 
+EINSUM_LOAD_MODES = ("KFAST", "KVEC", "ROWS", "ROWVEC")       # CPLXAMD_EINSUM_LOAD_*
+
+
+def einsum_dispatch(desc, addresses, dtype):
+    """What cplxamd_ceinsum decides on the host for descriptor `desc`, the four operand plane addresses (a_r, a_i, b_r, b_i:
+    integers, only their alignment is looked at) and a dtype code, without a GPU (cplxamd_einsum_plan):
+    -> dict(mode_a, mode_b: names of EINSUM_LOAD_MODES as they hold after the swap, swapped, tile, grid)."""
+    out = (ctypes.c_int64 * 5)()
+    call("cplxamd_einsum_plan", ctypes.byref(desc), *(int(a) for a in addresses), int(dtype), out)
+    return dict(mode_a=EINSUM_LOAD_MODES[out[0]], mode_b=EINSUM_LOAD_MODES[out[1]], swapped=bool(out[2]), tile=int(out[3]),
+                grid=int(out[4]))
+
+
 def ceinsum(ar, ai, br, bi, plan):
     """C = contraction of op(A) and op(B) as `plan` (cplxmodule_amd.einsum.Plan) says, in ONE launch; C is allocated
     contiguous in the plan's output order."""

@@ -992,6 +992,20 @@ typedef struct cplxamd_einsum_desc {
 } cplxamd_einsum_desc;   /* 912 bytes */
 int cplxamd_ceinsum(const void* a_r, const void* a_i, const void* b_r, const void* b_i, void* c_r, void* c_i,
                     const cplxamd_einsum_desc* d, int conj_a, int conj_b, int in_dtype, int out_dtype, void* stream);
+/* The host-side decisions of cplxamd_ceinsum as a pure function (no GPU call; cplxamd_ceinsum itself goes through it):
+ * for descriptor `d`, operand plane ADDRESSES a_r .. b_i (only their low four bits are looked at, nothing is
+ * dereferenced) and dtype = in_dtype = out_dtype, writes plan[CPLXAMD_EINSUM_PLAN_*]: the load mode of each operand
+ * (CPLXAMD_EINSUM_LOAD_*: KFAST scalar loads along k, KVEC 16-byte loads along k, ROWS scalar loads along the rows, ROWVEC
+ * 16-byte loads along the rows, bf16 only), whether the operands and the M / N groups were swapped (C's unit stride lies in
+ * an M mode), the tile edge (64 | 128) and the number of workgroups (0: an empty result, no launch).  The modes are those
+ * AFTER the swap: MODE_A is the mode of the operand the kernel loads as A, i.e. of the caller's B when SWAPPED is 1.
+ * Returns what cplxamd_ceinsum returns for the same descriptor and dtype (CPLXAMD_EINVAL also for a NULL `plan`).
+ * A new export under ABI 25: nothing existing changes. */
+enum { CPLXAMD_EINSUM_LOAD_KFAST = 0, CPLXAMD_EINSUM_LOAD_KVEC = 1, CPLXAMD_EINSUM_LOAD_ROWS = 2, CPLXAMD_EINSUM_LOAD_ROWVEC = 3 };
+enum { CPLXAMD_EINSUM_PLAN_MODE_A = 0, CPLXAMD_EINSUM_PLAN_MODE_B = 1, CPLXAMD_EINSUM_PLAN_SWAPPED = 2,
+       CPLXAMD_EINSUM_PLAN_TILE = 3, CPLXAMD_EINSUM_PLAN_GRID = 4, CPLXAMD_EINSUM_PLAN_SIZE = 5 };
+int cplxamd_einsum_plan(const cplxamd_einsum_desc* d, uint64_t a_r, uint64_t a_i, uint64_t b_r, uint64_t b_i, int dtype,
+                        int64_t* plan);
 
 /* Complex abs-max pooling (cplx.max_poolnd, cplx.py:1114-1175): in every window the element of
  * largest modulus keeps both its parts (first maximum in row-major window order, as torch).
