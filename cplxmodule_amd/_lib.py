@@ -202,6 +202,10 @@ SIGNATURES = {
     "cplxamd_conv3d_dgrad": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "cplxamd_conv3d_wgrad_ws_bytes": [_P],
     "cplxamd_conv3d_wgrad": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P],
+    # still ABI 25: the Fourier transforms behind cplx.fft / ifft / fft2 / fftn (csrc/fft.hip; the descriptor is a host
+    # struct, FftDesc)
+    "cplxamd_fft_plan": [_L, _L, _I, _P, _P],
+    "cplxamd_fft": [_P, _P, _P, _P, _P, _I, _I, _P, _L, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -212,6 +216,13 @@ class EinsumDesc(ctypes.Structure):
     """cplxamd_einsum_desc: groups batch, M, N, K; mode 0 of a group is the outermost."""
     _fields_ = [("nmodes", ctypes.c_int32 * 4), ("extent", (ctypes.c_int32 * 8) * 4), ("stride_a", (c_int64 * 8) * 4),
                 ("stride_b", (c_int64 * 8) * 4), ("stride_c", (c_int64 * 8) * 4)]
+
+
+class FftDesc(ctypes.Structure):
+    """cplxamd_fft_desc: one transformed dim (n, n_in, element strides) and up to three batch runs, run 0 outermost."""
+    _fields_ = [("n", c_int64), ("n_in", c_int64), ("x_es", c_int64), ("y_es", c_int64), ("runs", ctypes.c_int32),
+                ("inverse", ctypes.c_int32), ("size", c_int64 * 3), ("x_stride", c_int64 * 3), ("y_stride", c_int64 * 3),
+                ("scale", c_double)]
 
 
 # function codes of cplxamd_cplx_fn_fwd / _bwd (CPLXAMD_FN_*)

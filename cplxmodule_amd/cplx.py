@@ -699,6 +699,58 @@ def tanh(input):
     return _elementary(input, "tanh")
 
 
+# ---- Fourier transforms (not in the reference; signatures, shapes, n / s and norm as torch.fft): one launch of the
+# package's own FFT kernels per transformed dim (cplxmodule_amd/fft.py, csrc/fft.hip) --------------------------------------
+def _fourier(input, s, dim, norm, inverse, name):
+    from . import fft as _fft
+    return Cplx(*_fft.fftn(input, s, dim, norm, inverse, name))
+
+
+def fft(input, n=None, dim=-1, norm=None):
+    r"""Discrete Fourier transform X_k = sum_j x_j e^{-2 pi i jk/n} along `dim` of a `Cplx`, as `torch.fft.fft`: `n` pads
+    with zeros or truncates, `norm` is None / "backward" (no scaling), "ortho" (1 / sqrt n) or "forward" (1 / n).  Planes
+    of float32, bfloat16 (float32 arithmetic, one rounding) or float64 on the device; the result has the input's dtype
+    and memory order.  Any length up to 2^22; differentiable to any order."""
+    return _fourier(input, None if n is None else [n], [dim], norm, False, "fft")
+
+
+def ifft(input, n=None, dim=-1, norm=None):
+    r"""Inverse transform x_j = 1/n sum_k X_k e^{+2 pi i jk/n} along `dim`, as `torch.fft.ifft` (`norm` names the
+    direction that carries the 1 / n, as there)."""
+    return _fourier(input, None if n is None else [n], [dim], norm, True, "ifft")
+
+
+def fft2(input, s=None, dim=(-2, -1), norm=None):
+    """Two-dimensional transform, as `torch.fft.fft2`: one launch per dim, the last listed dim first; bf16 planes keep
+    a float32 intermediate and round once."""
+    return _fourier(input, s, dim, norm, False, "fft2")
+
+
+def ifft2(input, s=None, dim=(-2, -1), norm=None):
+    """Inverse of `fft2`, as `torch.fft.ifft2`."""
+    return _fourier(input, s, dim, norm, True, "ifft2")
+
+
+def fftn(input, s=None, dim=None, norm=None):
+    """N-dimensional transform, as `torch.fft.fftn`: over all dims, the last len(s), or those in `dim`."""
+    return _fourier(input, s, dim, norm, False, "fftn")
+
+
+def ifftn(input, s=None, dim=None, norm=None):
+    """Inverse of `fftn`, as `torch.fft.ifftn`."""
+    return _fourier(input, s, dim, norm, True, "ifftn")
+
+
+def fftshift(input, dim=None):
+    """`torch.fft.fftshift` on each plane (plumbing: any device)."""
+    return Cplx(torch.fft.fftshift(input.real, dim=dim), torch.fft.fftshift(input.imag, dim=dim))
+
+
+def ifftshift(input, dim=None):
+    """`torch.fft.ifftshift` on each plane (plumbing: any device)."""
+    return Cplx(torch.fft.ifftshift(input.real, dim=dim), torch.fft.ifftshift(input.imag, dim=dim))
+
+
 def modrelu(input, threshold=0.5):
     """Soft-threshold of the modulus, phase kept: z * relu(1 - threshold / max(|z|, 1e-5))
     (cplxmodule/cplx.py:565-616; note the reference's flipped sign convention).  `threshold` is a

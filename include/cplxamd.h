@@ -964,6 +964,43 @@ int cplxamd_welch_bwd(const void* x_r, const void* x_i, int64_t x_row_stride, in
                       void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Discrete Fourier transforms of planar complex tensors (cplx.fft / ifft / fft2 / fftn; csrc/fft.hip on the engine of
+ * csrc/fft_engine.h, which the Welch spectra share).  New exports under ABI 25: nothing existing changes.
+ *   y[v][k] = scale * sum_{j < n_in} x[v][j] e^{-+ 2 pi i j k / n},  k in [0, n),  for every vector v of the batch.
+ * Element j of vector v = (i0, i1, i2) lies at x_r / x_i [sum_r i_r x_stride[r] + j x_es], output k at y_r / y_i
+ * [sum_r i_r y_stride[r] + k y_es]: element strides, 64-bit offsets, `runs` batch runs with run 0 outermost (the vectors
+ * one workgroup transforms together are consecutive in the LAST run).  x strides may be zero (broadcast); x and y must
+ * not overlap, and distinct outputs must not alias.  Elements n_in .. n - 1 of a vector are zeros and are never loaded.
+ * Dtype pairs (in, out): (F32, F32), (BF16, BF16), (BF16, F32), (F32, BF16), (F64, F64); bf16 is widened on load, the
+ * arithmetic is float32 (float64 for F64), and every output is rounded once, on store.  The transform is unnormalised:
+ * `scale` multiplies the result before that rounding.
+ * cplxamd_fft_plan is a pure function (no GPU): it returns the path (CPLXAMD_WELCH_*; DIRECT / BLUESTEIN here mean "inside
+ * one workgroup's LDS", the FOURSTEP codes "through the workspace") of a length-n transform of `vectors` vectors whose
+ * INPUT dtype is `dtype`, how many vectors one workgroup transforms (2048 / M for a packed M = 2^k in [8, 1024], 256 below
+ * 8, else 1; M = n, or Bluestein's 2^ceil(log2(2n - 1))), and the workspace bytes (nullable outputs); CPLXAMD_EINVAL for
+ * n outside [1, CPLXAMD_WELCH_MAX_N], negative `vectors` or a bad dtype.  cplxamd_fft goes through the same plan and
+ * checks every argument before any launch: CPLXAMD_EINVAL (NULL pointer -- the workspace included --, bad dtype pair, n /
+ * n_in / strides / runs / sizes out of range, unknown bits in `inverse`, a scale that is not finite), CPLXAMD_ESHAPE
+ * (more than 2^31 - 1 vectors), CPLXAMD_EWS (workspace smaller than the plan's).  Zero vectors: no launch, returns 0.
+ * The tables of a call (twiddles, chirp, B-hat) are built in its workspace: no state in the library, no atomics, the same
+ * input gives the same bits, capturable in a hipGraph.
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_FFT_INVERSE = 1,              /* e^{+2 pi i jk/n}, unnormalised                                          */
+       CPLXAMD_FFT_ONE_PER_WORKGROUP = 2     /* measurement only: run a packed length with one vector per workgroup     */ };
+typedef struct cplxamd_fft_desc {
+  int64_t n;            /* transform length, 1 .. 2^22 (CPLXAMD_WELCH_MAX_N) */
+  int64_t n_in;         /* inputs read per vector, 1 .. n; elements n_in .. n-1 are zeros (never loaded) */
+  int64_t x_es, y_es;   /* element strides along the transformed dim, in elements; x_es may be any value >= 0, y_es >= 1 */
+  int32_t runs;         /* 0 .. 3 batch runs, run 0 outermost */
+  int32_t inverse;      /* 0: e^{-2 pi i jk/n}; 1: e^{+2 pi i jk/n} (unnormalised); CPLXAMD_FFT_* bits */
+  int64_t size[3], x_stride[3], y_stride[3];
+  double  scale;        /* multiplies the result in the epilogue, before its one rounding */
+} cplxamd_fft_desc;     /* 120 bytes */
+int cplxamd_fft_plan(int64_t n, int64_t vectors, int dtype, int* vectors_per_workgroup, int64_t* ws_bytes);
+int cplxamd_fft(const void* x_r, const void* x_i, void* y_r, void* y_i, const cplxamd_fft_desc* d,
+                int in_dtype, int out_dtype, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Strided complex tensor contraction (cplx.einsum with two operands, cplxmodule/cplx.py:1032-1059; csrc/einsum.hip).  A new
  * export under ABI 25: nothing existing changes.
  *   C[b.., m.., n..] = sum_{k..} op(A)[b.., m.., k..] * op(B)[b.., n.., k..],   op = identity or conjugate per operand
