@@ -206,6 +206,9 @@ SIGNATURES = {
     # struct, FftDesc)
     "cplxamd_fft_plan": [_L, _L, _I, _P, _P],
     "cplxamd_fft": [_P, _P, _P, _P, _P, _I, _I, _P, _L, _P],
+    # still ABI 25: the real-input / real-output transforms behind cplx.rfft / irfft / hfft / ihfft (csrc/rfft.hip)
+    "cplxamd_rfft_plan": [_L, _L, _I, _I, _P, _P, _P, _P],
+    "cplxamd_rfft": [_P, _P, _P, _P, _P, _I, _I, _P, _L, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)

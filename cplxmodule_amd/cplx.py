@@ -741,6 +741,66 @@ def ifftn(input, s=None, dim=None, norm=None):
     return _fourier(input, s, dim, norm, True, "ifftn")
 
 
+# ---- real-input / real-output transforms (as torch.fft's): an even length runs ONE complex transform of half the
+# length plus an untangling pass, on the same engine (cplxmodule_amd/rfft.py, csrc/rfft.hip) ------------------------------
+def _one(n):
+    return None if n is None else [n]
+
+
+def rfft(input, n=None, dim=-1, norm=None):
+    r"""X_k = sum_j x_j e^{-2 pi i jk/n}, k = 0 .. n // 2, of a REAL tensor along `dim`, as `torch.fft.rfft` -> `Cplx` whose
+    planes have the input's dtype (float32, bfloat16 or float64) and memory order.  No zero plane is built and only the
+    half spectrum is computed and written.  Differentiable to any order (the gradient is not `irfft`: see rfft.py)."""
+    from . import rfft as _rfft
+    return Cplx(*_rfft.rfftn(input, _one(n), [dim], norm, False, "rfft"))
+
+
+def irfft(input, n=None, dim=-1, norm=None):
+    r"""Inverse of `rfft`, as `torch.fft.irfft`: a `Cplx` half spectrum -> a real tensor of length `n` (default 2 (m - 1))
+    along `dim`; the first n // 2 + 1 entries are used (zero-padded if fewer), the imaginary parts of the DC and, for
+    even n, the Nyquist entry are ignored."""
+    from . import rfft as _rfft
+    return _rfft.irfftn(input, _one(n), [dim], norm, True, "irfft")
+
+
+def rfft2(input, s=None, dim=(-2, -1), norm=None):
+    """`torch.fft.rfft2`: the real transform along the last listed dim, then the complex one along the other."""
+    from . import rfft as _rfft
+    return Cplx(*_rfft.rfftn(input, s, dim, norm, False, "rfft2"))
+
+
+def irfft2(input, s=None, dim=(-2, -1), norm=None):
+    """`torch.fft.irfft2`: the complex inverse along the first listed dim, then the real-output one along the last."""
+    from . import rfft as _rfft
+    return _rfft.irfftn(input, s, dim, norm, True, "irfft2")
+
+
+def rfftn(input, s=None, dim=None, norm=None):
+    """`torch.fft.rfftn`: over all dims, the last len(s), or those in `dim`; the half spectrum lies along the last one."""
+    from . import rfft as _rfft
+    return Cplx(*_rfft.rfftn(input, s, dim, norm, False, "rfftn"))
+
+
+def irfftn(input, s=None, dim=None, norm=None):
+    """`torch.fft.irfftn`: the inverse of `rfftn`; the last entry of `s` is the real output's length (default 2 (m - 1))."""
+    from . import rfft as _rfft
+    return _rfft.irfftn(input, s, dim, norm, True, "irfftn")
+
+
+def hfft(input, n=None, dim=-1, norm=None):
+    r"""`torch.fft.hfft`: the transform of a Hermitian signal given by its half (`Cplx`) -> its real spectrum of length
+    `n` (default 2 (m - 1)): `irfft`'s kernel with the opposite sign and the forward transform's scaling."""
+    from . import rfft as _rfft
+    return _rfft.irfftn(input, _one(n), [dim], norm, False, "hfft")
+
+
+def ihfft(input, n=None, dim=-1, norm=None):
+    r"""`torch.fft.ihfft`: a real tensor -> the half (`Cplx`) of its Hermitian inverse transform: `rfft`'s kernel with the
+    opposite sign and the inverse transform's scaling."""
+    from . import rfft as _rfft
+    return Cplx(*_rfft.rfftn(input, _one(n), [dim], norm, True, "ihfft"))
+
+
 def fftshift(input, dim=None):
     """`torch.fft.fftshift` on each plane (plumbing: any device)."""
     return Cplx(torch.fft.fftshift(input.real, dim=dim), torch.fft.fftshift(input.imag, dim=dim))

@@ -6,7 +6,7 @@
 // of a vector are zeros that are never loaded (zero padding costs no copy).  bf16 planes are widened on load, the
 // arithmetic is float32 (float64 for float64 planes), and every output is rounded once, on store.
 //
-// Paths (fft_plan; the codes are Welch's):
+// Paths (fft_plan_t in fft_engine.h, which rfft.hip shares; the codes are Welch's):
 //   packed      M = 2^k <= 1024 points (M = n, or Bluestein's M = 2^ceil(log2(2n - 1))): a 256-thread workgroup transforms
 //               V = 256 / kNT<k> vectors (2048 / M; 256 for M < 8), vector threadIdx.x / kNT on lane threadIdx.x % kNT and
 //               its own LDS slice.  The V vectors are consecutive in the innermost run.  Along the last dim the engine's
@@ -30,22 +30,6 @@
 
 namespace cplxamd {
 namespace sp {
-
-constexpr int kPackT = 256;                               // threads of a packed workgroup
-constexpr int kLogPackMax = 10;                           // packed up to 1024 points
-template <int LOGM> constexpr int kVecs = kPackT / kNT<LOGM>;
-// words of one vector's LDS slice in a packed workgroup: odd
-template <int LOGM> constexpr int kSlice = 2 * (pad(1 << LOGM) + 1) + 1;
-
-// the batch of a call: three runs (unused ones have size 1), run 2 innermost
-struct Batch {
-  int64_t total, s1, s2, xs[3], ys[3];
-};
-__device__ __forceinline__ void batch_offsets(const Batch& b, int64_t v, int64_t& xo, int64_t& yo) {
-  const int64_t i2 = v % b.s2, q = v / b.s2, i1 = q % b.s1, i0 = q / b.s1;
-  xo = i0 * b.xs[0] + i1 * b.xs[1] + i2 * b.xs[2];
-  yo = i0 * b.ys[0] + i1 * b.ys[1] + i2 * b.ys[2];
-}
 
 template <typename TI, typename TO, typename T>
 struct Io {
@@ -166,13 +150,6 @@ __global__ __launch_bounds__(kET) void fft_gather(Io<TI, TO, T> io, Batch b, int
   }
 }
 
-// buf[v][k] *= h[k] (conj: conj(h[k]))
-template <typename T>
-__global__ __launch_bounds__(kET) void fft_mul(C2<T>* buf, int64_t nv, int64_t M, const C2<T>* h, bool conj) {
-  for (int64_t i = (int64_t)blockIdx.x * kET + threadIdx.x; i < nv * M; i += (int64_t)gridDim.x * kET)
-    buf[i] = conj ? cmulc(buf[i], h[i % M]) : cmul(buf[i], h[i % M]);
-}
-
 // y[v0 + v][k] = buf[v][k] (closing chirp, scale, one rounding), k in [0, n)
 template <typename TI, typename TO, typename T, bool BLUE>
 __global__ __launch_bounds__(kET) void fft_scatter(Io<TI, TO, T> io, Batch b, int64_t v0, int64_t nv, int64_t M,
@@ -183,59 +160,6 @@ __global__ __launch_bounds__(kET) void fft_scatter(Io<TI, TO, T> io, Batch b, in
     batch_offsets(b, v0 + v, xo, yo);
     io.template out<BLUE>(yo, k, buf[v * M + k]);
   }
-}
-
-// ---- plan --------------------------------------------------------------------------------------------------------------
-struct FftPlan {
-  int path, logM, vpw;                  // vpw: vectors per workgroup (1 unless packed)
-  bool blue, lds;                       // lds: the whole transform inside one workgroup's LDS
-  int64_t M, GL;                        // through the workspace: GL vectors per batch
-  int64_t off_tw, off_chirp, off_bhat, off_buf, off_tmp, bytes;
-};
-
-template <typename T>
-int fft_plan_t(int64_t n, int64_t vectors, FftPlan& p) {
-  if (n < 1 || n > CPLXAMD_WELCH_MAX_N || vectors < 0) return CPLXAMD_EINVAL;
-  const bool pow2 = (n & (n - 1)) == 0;
-  int64_t M = 1;
-  if (pow2) M = n;
-  else while (M < 2 * n - 1) M <<= 1;
-  p.M = M;
-  p.logM = 63 - __builtin_clzll((unsigned long long)M);
-  p.blue = !pow2;
-  p.lds = pow2 ? p.logM <= kLogLMax<T> : p.logM <= kLogFusedMax;
-  p.path = (pow2 ? CPLXAMD_WELCH_DIRECT : CPLXAMD_WELCH_BLUESTEIN) + (p.lds ? 0 : 1);
-  const int64_t nt = M / 8 > 0 ? M / 8 : 1;               // kNT of a packed length
-  p.vpw = p.lds && p.logM <= kLogPackMax ? (int)(kPackT / nt) : 1;
-  const int64_t cs = sizeof(C2<T>);
-  int64_t off = 0;
-  p.off_tw = off;
-  off += al256(M * cs);
-  p.off_chirp = p.off_bhat = off;
-  if (p.blue) {
-    off += al256(n * cs);
-    p.off_bhat = off;
-    off += al256(M * cs);
-  }
-  p.off_buf = p.off_tmp = off;
-  p.GL = 1;
-  if (!p.lds) {                                           // batches bounded as Welch's
-    int64_t GL = kLargeWs / (2 * M * cs);
-    if (GL < 1) GL = 1;
-    if (GL > vectors) GL = vectors > 0 ? vectors : 1;
-    if (GL > 65535) GL = 65535;
-    p.GL = GL;
-    p.off_tmp = off + al256(GL * M * cs);
-    off = p.off_tmp + al256(GL * M * cs);
-  }
-  p.bytes = off;
-  return 0;
-}
-
-inline int fft_plan_for(int64_t n, int64_t vectors, int dtype, FftPlan& p) {
-  if (dtype == CPLXAMD_F64) return fft_plan_t<double>(n, vectors, p);
-  if (dtype == CPLXAMD_F32 || dtype == CPLXAMD_BF16) return fft_plan_t<float>(n, vectors, p);
-  return CPLXAMD_EINVAL;
 }
 
 template <typename TI, typename TO, typename T, bool BLUE, int LOGM, int V, bool STAGED>
@@ -339,18 +263,8 @@ int cplxamd_fft(const void* x_r, const void* x_i, void* y_r, void* y_i, const cp
   if (d->n < 1 || d->n > CPLXAMD_WELCH_MAX_N || d->n_in < 1 || d->n_in > d->n || d->x_es < 0 || d->y_es < 1 || d->runs < 0 ||
       d->runs > 3 || (d->inverse & ~(CPLXAMD_FFT_INVERSE | CPLXAMD_FFT_ONE_PER_WORKGROUP)) || !(d->scale - d->scale == 0))
     return CPLXAMD_EINVAL;
-  Batch b{1, 1, 1, {0, 0, 0}, {0, 0, 0}};
-  int64_t size[3] = {1, 1, 1};
-  for (int r = 0; r < d->runs; ++r) {                     // right-aligned: the innermost run is run 2
-    const int s = 3 - d->runs + r;
-    if (d->size[r] < 0) return CPLXAMD_EINVAL;
-    size[s] = d->size[r];
-    b.xs[s] = d->x_stride[r];
-    b.ys[s] = d->y_stride[r];
-    if (__builtin_mul_overflow(b.total, d->size[r], &b.total)) return CPLXAMD_ESHAPE;
-  }
-  b.s1 = size[1] > 0 ? size[1] : 1;
-  b.s2 = size[2] > 0 ? size[2] : 1;
+  Batch b;
+  if (const int e = batch_of(*d, b)) return e;
   FftPlan p;
   if (const int e = fft_plan_for(d->n, b.total, in_dtype, p)) return e;
   if (b.total > 0x7fffffffll) return CPLXAMD_ESHAPE;     // workgroups are indexed by one grid dimension

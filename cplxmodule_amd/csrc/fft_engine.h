@@ -1,6 +1,7 @@
 // The package's FFT engine: a Stockham FFT of a power-of-two length held by one workgroup (or one slice of one), the
 // batched pass kernel and the four-step driver built on it, and the per-call tables.  Shared by the Welch spectra
-// (spectrum.hip, which describes the engine and the size classes at its top) and the transforms themselves (fft.hip).
+// (spectrum.hip, which describes the engine and the size classes at its top) and the transforms themselves (fft.hip,
+// rfft.hip), whose batch, plan and packing constants stand at the end.
 //
 // Engine (fft_run): compiled per length 2^LOGL <= 2^kLogLMax: every stage, stride and thread count is a compile-time
 // constant.  kNT<LOGL> threads hold kEOf<LOGL> values each; radix-8 butterflies (one leading radix-2 / 4 stage when 3 does
@@ -303,6 +304,100 @@ int fft_vectors(int logM, const C2<T>* tw, C2<T>* buf, C2<T>* tmp, int64_t nv, T
   if (const int e = launch_pass<T>(logN1, dim3(N2, nv), buf, tmp, M, 1, N2, 1, N2, tw, logM, true, sg, st)) return e;
   // rows: FFT over n2 of tmp[k1 N2 + n2], to buf[k1 + N1 k2]
   return launch_pass<T>(logN2, dim3(N1, nv), tmp, buf, M, N2, 1, 1, N1, tw, logM, false, sg, st);
+}
+
+// ---- shared by the transforms of fft.hip and rfft.hip: the packed workgroup, the batch, the plan ---------------------------
+constexpr int kPackT = 256;                               // threads of a packed workgroup
+constexpr int kLogPackMax = 10;                           // packed up to 1024 points
+template <int LOGM> constexpr int kVecs = kPackT / kNT<LOGM>;
+// words of one vector's LDS slice in a packed workgroup: odd
+template <int LOGM> constexpr int kSlice = 2 * (pad(1 << LOGM) + 1) + 1;
+
+// the batch of a call: three runs (unused ones have size 1), run 2 innermost
+struct Batch {
+  int64_t total, s1, s2, xs[3], ys[3];
+};
+__device__ __forceinline__ void batch_offsets(const Batch& b, int64_t v, int64_t& xo, int64_t& yo) {
+  const int64_t i2 = v % b.s2, q = v / b.s2, i1 = q % b.s1, i0 = q / b.s1;
+  xo = i0 * b.xs[0] + i1 * b.xs[1] + i2 * b.xs[2];
+  yo = i0 * b.ys[0] + i1 * b.ys[1] + i2 * b.ys[2];
+}
+
+// the batch of a descriptor: its runs right-aligned (the innermost run is run 2)
+inline int batch_of(const cplxamd_fft_desc& d, Batch& b) {
+  b = Batch{1, 1, 1, {0, 0, 0}, {0, 0, 0}};
+  int64_t size[3] = {1, 1, 1};
+  for (int r = 0; r < d.runs; ++r) {
+    const int s = 3 - d.runs + r;
+    if (d.size[r] < 0) return CPLXAMD_EINVAL;
+    size[s] = d.size[r];
+    b.xs[s] = d.x_stride[r];
+    b.ys[s] = d.y_stride[r];
+    if (__builtin_mul_overflow(b.total, d.size[r], &b.total)) return CPLXAMD_ESHAPE;
+  }
+  b.s1 = size[1] > 0 ? size[1] : 1;
+  b.s2 = size[2] > 0 ? size[2] : 1;
+  return 0;
+}
+
+// buf[v][k] *= h[k] (conj: conj(h[k]))
+template <typename T>
+__global__ __launch_bounds__(kET) void fft_mul(C2<T>* buf, int64_t nv, int64_t M, const C2<T>* h, bool conj) {
+  for (int64_t i = (int64_t)blockIdx.x * kET + threadIdx.x; i < nv * M; i += (int64_t)gridDim.x * kET)
+    buf[i] = conj ? cmulc(buf[i], h[i % M]) : cmul(buf[i], h[i % M]);
+}
+
+// ---- plan --------------------------------------------------------------------------------------------------------------
+struct FftPlan {
+  int path, logM, vpw;                  // vpw: vectors per workgroup (1 unless packed)
+  bool blue, lds;                       // lds: the whole transform inside one workgroup's LDS
+  int64_t M, GL;                        // through the workspace: GL vectors per batch
+  int64_t off_tw, off_chirp, off_bhat, off_buf, off_tmp, bytes;
+};
+
+template <typename T>
+int fft_plan_t(int64_t n, int64_t vectors, FftPlan& p) {
+  if (n < 1 || n > CPLXAMD_WELCH_MAX_N || vectors < 0) return CPLXAMD_EINVAL;
+  const bool pow2 = (n & (n - 1)) == 0;
+  int64_t M = 1;
+  if (pow2) M = n;
+  else while (M < 2 * n - 1) M <<= 1;
+  p.M = M;
+  p.logM = 63 - __builtin_clzll((unsigned long long)M);
+  p.blue = !pow2;
+  p.lds = pow2 ? p.logM <= kLogLMax<T> : p.logM <= kLogFusedMax;
+  p.path = (pow2 ? CPLXAMD_WELCH_DIRECT : CPLXAMD_WELCH_BLUESTEIN) + (p.lds ? 0 : 1);
+  const int64_t nt = M / 8 > 0 ? M / 8 : 1;               // kNT of a packed length
+  p.vpw = p.lds && p.logM <= kLogPackMax ? (int)(kPackT / nt) : 1;
+  const int64_t cs = sizeof(C2<T>);
+  int64_t off = 0;
+  p.off_tw = off;
+  off += al256(M * cs);
+  p.off_chirp = p.off_bhat = off;
+  if (p.blue) {
+    off += al256(n * cs);
+    p.off_bhat = off;
+    off += al256(M * cs);
+  }
+  p.off_buf = p.off_tmp = off;
+  p.GL = 1;
+  if (!p.lds) {                                           // batches bounded as Welch's
+    int64_t GL = kLargeWs / (2 * M * cs);
+    if (GL < 1) GL = 1;
+    if (GL > vectors) GL = vectors > 0 ? vectors : 1;
+    if (GL > 65535) GL = 65535;
+    p.GL = GL;
+    p.off_tmp = off + al256(GL * M * cs);
+    off = p.off_tmp + al256(GL * M * cs);
+  }
+  p.bytes = off;
+  return 0;
+}
+
+inline int fft_plan_for(int64_t n, int64_t vectors, int dtype, FftPlan& p) {
+  if (dtype == CPLXAMD_F64) return fft_plan_t<double>(n, vectors, p);
+  if (dtype == CPLXAMD_F32 || dtype == CPLXAMD_BF16) return fft_plan_t<float>(n, vectors, p);
+  return CPLXAMD_EINVAL;
 }
 
 }  // namespace sp

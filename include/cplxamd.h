@@ -1001,6 +1001,30 @@ int cplxamd_fft(const void* x_r, const void* x_i, void* y_r, void* y_i, const cp
                 int in_dtype, int out_dtype, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Real-input and real-output transforms (cplx.rfft / irfft / rfft2 / rfftn / hfft / ihfft; csrc/rfft.hip on the same
+ * engine, batch and descriptor).  New exports under ABI 25: nothing existing changes, cplxamd_fft rejects the bits below.
+ * With h = n / 2, w_k = 1 for k = 0 and (n even) k = h, else 2, and the sign of CPLXAMD_FFT_INVERSE:
+ *   R2C (default)       y[v][k] = scale [w_k] sum_{j < n_in} x[v][j] e^{-+ 2 pi i jk/n},  k in [0, h];  n_in <= n reals of
+ *                       x_r are read (x_i is not looked at and may be NULL); Im y_0 and (n even) Im y_h are stored as 0.
+ *                       CPLXAMD_RFFT_WEIGHTED multiplies by w_k (the adjoint of the Hermitian extension).
+ *   CPLXAMD_RFFT_C2R    y[v][j] = scale Re sum_{k < n_in} c_k X[v][k] e^{-+ 2 pi i jk/n},  j in [0, n);  n_in <= h + 1
+ *                       entries of x_r / x_i are read, Im X_0 and (n even) Im X_h are ignored; y_r alone is written (y_i
+ *                       may be NULL).  c_k = w_k with CPLXAMD_RFFT_WEIGHTED (the transform of the Hermitian extension:
+ *                       irfft, hfft), c_k = 1 without (the adjoint of R2C).
+ * `n` of the descriptor is the REAL length in both directions.  Even n runs one complex transform of h points (packing
+ * before, untangling after), odd n of n points; dtype pairs, strides, runs, rounding, errors and the workspace rules are
+ * cplxamd_fft's.  cplxamd_rfft_plan is a pure function: the path of that complex transform (CPLXAMD_WELCH_*), its length
+ * (`complex_n`: h or n), the power of two actually run (`points`: complex_n, or Bluestein's M), the vectors per
+ * workgroup and the workspace bytes, which include the table e^{-2 pi i k/n}, k < h (nullable outputs); `c2r` is 0 or 1.
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_RFFT_C2R = 4,                 /* half spectrum in, reals out (default: reals in, half spectrum out)      */
+       CPLXAMD_RFFT_WEIGHTED = 8             /* R2C: outputs times w_k; C2R: c_k = w_k (Hermitian extension)            */ };
+int cplxamd_rfft_plan(int64_t n, int64_t vectors, int dtype, int c2r, int64_t* complex_n, int64_t* points,
+                      int* vectors_per_workgroup, int64_t* ws_bytes);
+int cplxamd_rfft(const void* x_r, const void* x_i, void* y_r, void* y_i, const cplxamd_fft_desc* d,
+                 int in_dtype, int out_dtype, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Strided complex tensor contraction (cplx.einsum with two operands, cplxmodule/cplx.py:1032-1059; csrc/einsum.hip).  A new
  * export under ABI 25: nothing existing changes.
  *   C[b.., m.., n..] = sum_{k..} op(A)[b.., m.., k..] * op(B)[b.., n.., k..],   op = identity or conjugate per operand
