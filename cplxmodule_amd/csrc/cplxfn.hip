@@ -5,13 +5,16 @@
 //
 // Numerics: float32 arithmetic for both dtypes (bf16 is widened on load and rounded once on store), full-precision
 // device math (sincosf / expf / expm1f / tanf / atan2f / log1pf, not the __expf-style intrinsics), and forms that
-// neither cancel nor overflow where the true value is representable:
-//   exp   e^x (cos y, sin y)
+// neither cancel nor overflow where the true value is representable -- per PART: e^x cos y is finite for x well past
+// 88.72 (where e^x overflows) when y is near an odd multiple of pi / 2, so past 88 the exponential enters as two
+// factors e^{x/2} with the trigonometric factor multiplied in between them:
+//   exp   e^x (cos y, sin y);  x > 88: (e^{x/2} cos y) e^{x/2}, (e^{x/2} sin y) e^{x/2}
 //   log   (log|z|, atan2(y, x)), log|z| = log a + log1p((b / a)^2) / 2 with a = max(|x|, |y|), b = min: no overflow or
 //         underflow anywhere in the float32 range; log 0 = -inf + i atan2(y, x)
 //   sin   (sin x cosh y,  cos x sinh y)      cos  (cos x cosh y, -sin x sinh y)
 //   sinh  (sinh x cos y,  cosh x sin y)      cosh (cosh x cos y,  sinh x sin y)
-//         cosh / sinh of a real argument from ONE expm1f (e = 1 + expm1 t), so sinh stays accurate for |t| < 1
+//         cosh / sinh of a real argument from ONE expm1f (e = 1 + expm1 t), so sinh stays accurate for |t| < 1;
+//         |t| > 88: cosh t p = sinh |t| p = ((e^{|t|/2} / 2) p) e^{|t|/2} for the trigonometric factor p
 //   tanh  Kahan: t = tan y, s = sinh x, beta = 1 + t^2, rho = sqrt(1 + s^2):  (beta rho s + i t) / (1 + beta s^2);
 //         for |x| > kSat (tanh x rounds to +-1): (sign x, 4 sin y cos y e^{-2|x|})
 //   tan   -i tanh(iz)
@@ -19,6 +22,11 @@
 // sec^2 z, sech^2 z; sech^2 z = (conj(cosh z) / |cosh z|^2)^2 with |cosh z|^2 = sinh^2 x + cos^2 y, and past kSat
 // 4 e^{-2|x|} e^{-2 i sign(x) y} -- never 1 - tanh^2, which cancels where |f'| ~ 4 e^{-2|x|}.
 #include "common.h"
+
+// One rounding per written operation.  Left to contract a * b + c * d into a fused multiply-add, the compiler fuses the
+// unrolled vector body and the scalar tail of the kernel differently, and a value then depends (in its last bit) on where
+// in the tensor it stands; the accuracy statements above are for the unfused forms.
+#pragma clang fp contract(off)
 
 namespace cplxamd {
 
@@ -42,9 +50,29 @@ __device__ __forceinline__ void chsh(float t, float& c, float& s) {
   s = copysignf(s, t);
 }
 
+// (cosh t * p, sinh t * q): chsh followed by the two products for |t| <= 88 (the same bits); past it the factor goes in
+// before the second e^{|t|/2}, so a product that is representable is finite although cosh t alone is not
+__device__ __forceinline__ void chsh_mul(float t, float p, float q, float& cp, float& sq) {
+  const float a = fabsf(t);
+  if (a <= 88.0f) {
+    float c, s;
+    chsh(t, c, s);
+    cp = c * p;
+    sq = s * q;
+  } else {            // NaN lands here too
+    const float h = expf(0.5f * a), hh = 0.5f * h;
+    cp = (hh * p) * h;
+    sq = (copysignf(hh, t) * q) * h;
+  }
+}
+
 __device__ __forceinline__ CF f_exp(float x, float y) {
   float s, c;
   sincosf(y, &s, &c);
+  if (x > 88.0f) {    // e^x overflows at 88.72, e^x cos y need not
+    const float h = expf(0.5f * x);
+    return {(h * c) * h, (h * s) * h};
+  }
   const float e = expf(x);
   return {e * c, e * s};
 }
@@ -66,29 +94,29 @@ __device__ __forceinline__ CF f_log(float x, float y) {
 __device__ __forceinline__ CF f_sin(float x, float y) {
   float sx, cx, ch, sh;
   sincosf(x, &sx, &cx);
-  chsh(y, ch, sh);
-  return {sx * ch, cx * sh};
+  chsh_mul(y, sx, cx, ch, sh);
+  return {ch, sh};
 }
 
 __device__ __forceinline__ CF f_cos(float x, float y) {
   float sx, cx, ch, sh;
   sincosf(x, &sx, &cx);
-  chsh(y, ch, sh);
-  return {cx * ch, -(sx * sh)};
+  chsh_mul(y, cx, sx, ch, sh);
+  return {ch, -sh};
 }
 
 __device__ __forceinline__ CF f_sinh(float x, float y) {
   float sy, cy, ch, sh;
   sincosf(y, &sy, &cy);
-  chsh(x, ch, sh);
-  return {sh * cy, ch * sy};
+  chsh_mul(x, sy, cy, ch, sh);
+  return {sh, ch};
 }
 
 __device__ __forceinline__ CF f_cosh(float x, float y) {
   float sy, cy, ch, sh;
   sincosf(y, &sy, &cy);
-  chsh(x, ch, sh);
-  return {ch * cy, sh * sy};
+  chsh_mul(x, cy, sy, ch, sh);
+  return {ch, sh};
 }
 
 __device__ __forceinline__ CF f_tanh(float x, float y) {

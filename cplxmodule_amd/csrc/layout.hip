@@ -112,13 +112,15 @@ __global__ __launch_bounds__(kLT) void split_relu_kernel(const T* ar, const T* a
 }
 
 // modReLU with the reference's op order: m = max(|z|, 1e-5) (|z| = sqrt(fma(zi, zi, zr zr)), the CPU
-// kernel's form), s = max(1 - tau / m, 0), y = z s.  tau: scalar value, or a tensor of n elements.
+// kernel's form), s = max(1 - tau / m, 0), y = z s.  tau: scalar value, or a tensor of n elements.  clamp and relu pass a
+// NaN on, as torch's do (fmaxf would drop it, and a NaN in one part of z would leave the other part finite).
 struct ModRelu {
   float s, m, az;
   __device__ __forceinline__ ModRelu(float zr, float zi, float tau) {
     az = rn_sqrt(fmaf(zi, zi, zr * zr));
-    m = fmaxf(az, 1e-5f);
-    s = fmaxf(1.0f - tau / m, 0.0f);
+    m = az < 1e-5f ? 1e-5f : az;
+    const float pre = 1.0f - tau / m;
+    s = pre <= 0.0f ? 0.0f : pre;
   }
 };
 

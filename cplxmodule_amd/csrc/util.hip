@@ -295,6 +295,11 @@ __global__ __launch_bounds__(kUT) void mask_mul_kernel(const TI* ar, const TI* a
   }
 }
 
+// The streaming kernels above move 16 bytes per lane (ld4 / st4): every plane they are given is 16-byte aligned.  Checked
+// before any launch (CPLXAMD_EALIGN), NULL standing for an absent optional plane; n == 0 launches nothing.
+static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static bool ew_dtype(int d) { return d == CPLXAMD_F32 || d == CPLXAMD_BF16; }
+
 }  // namespace cplxamd
 
 using namespace cplxamd;
@@ -302,13 +307,17 @@ using namespace cplxamd;
 extern "C" {
 
 int cplxamd_cplx_abs_fwd(const void* xr, const void* xi, void* out, int64_t n, int dtype, void* stream) {
-  if (!xr || !xi || !out || n < 0) return CPLXAMD_EINVAL;
+  if (!xr || !xi || !out || n < 0 || !ew_dtype(dtype)) return CPLXAMD_EINVAL;
+  if (!al16(xr) || !al16(xi) || !al16(out)) return CPLXAMD_EALIGN;
+  if (n == 0) return 0;
   return launch_ew<4>(xr, xi, out, n, dtype, dtype, (hipStream_t)stream);
 }
 
 int cplxamd_cplx_abs_bwd(const void* g, const void* xr, const void* xi, void* dxr, void* dxi, int64_t n,
                          int dtype, void* stream) {
-  if (!g || !xr || !xi || !dxr || !dxi || n < 0) return CPLXAMD_EINVAL;
+  if (!g || !xr || !xi || !dxr || !dxi || n < 0 || !ew_dtype(dtype)) return CPLXAMD_EINVAL;
+  if (!al16(g) || !al16(xr) || !al16(xi) || !al16(dxr) || !al16(dxi)) return CPLXAMD_EALIGN;
+  if (n == 0) return 0;
   const int grid = stream_grid(n >> 2, kUT);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == CPLXAMD_F32)
@@ -325,7 +334,11 @@ int cplxamd_cplx_abs_bwd(const void* g, const void* xr, const void* xi, void* dx
 
 int cplxamd_mask_mul(const void* in_r, const void* in_i, const float* mask, void* out_r, void* out_i,
                      int64_t n, int in_dtype, int out_dtype, void* stream) {
-  if (!in_r || !mask || !out_r || n < 0 || ((in_i == nullptr) != (out_i == nullptr))) return CPLXAMD_EINVAL;
+  if (!in_r || !mask || !out_r || n < 0 || ((in_i == nullptr) != (out_i == nullptr)) || !ew_dtype(in_dtype) ||
+      !ew_dtype(out_dtype))
+    return CPLXAMD_EINVAL;
+  if (!al16(in_r) || !al16(in_i) || !al16(mask) || !al16(out_r) || !al16(out_i)) return CPLXAMD_EALIGN;
+  if (n == 0) return 0;
   const int grid = stream_grid(n >> 2, kUT);
   hipStream_t st = (hipStream_t)stream;
 #define MM(TI, TO) mask_mul_kernel<TI, TO><<<grid, kUT, 0, st>>>((const TI*)in_r, (const TI*)in_i, mask, (TO*)out_r, (TO*)out_i, n)
@@ -341,24 +354,32 @@ int cplxamd_mask_mul(const void* in_r, const void* in_i, const float* mask, void
 
 int cplxamd_abs2(const void* xr, const void* xi, void* out, int64_t n, int in_dtype,
                  int out_dtype, void* stream) {
-  if (!xr || !out || n < 0) return CPLXAMD_EINVAL;
+  if (!xr || !out || n < 0 || !ew_dtype(in_dtype) || !ew_dtype(out_dtype)) return CPLXAMD_EINVAL;
+  if (!al16(xr) || !al16(xi) || !al16(out)) return CPLXAMD_EALIGN;
+  if (n == 0) return 0;
   if (xi) return launch_ew<1>(xr, xi, out, n, in_dtype, out_dtype, (hipStream_t)stream);
   return launch_ew<2>(xr, nullptr, out, n, in_dtype, out_dtype, (hipStream_t)stream);
 }
 
 int cplxamd_modulus(const float* xr, const float* xi, float* out, int64_t n, void* stream) {
   if (!xr || !xi || !out || n < 0) return CPLXAMD_EINVAL;
+  if (!al16(xr) || !al16(xi) || !al16(out)) return CPLXAMD_EALIGN;
+  if (n == 0) return 0;
   return launch_ew<4>(xr, xi, out, n, CPLXAMD_F32, CPLXAMD_F32, (hipStream_t)stream);
 }
 
 int cplxamd_exp(const float* x, void* out, int64_t n, int out_dtype, void* stream) {
-  if (!x || !out || n < 0) return CPLXAMD_EINVAL;
+  if (!x || !out || n < 0 || !ew_dtype(out_dtype)) return CPLXAMD_EINVAL;
+  if (!al16(x) || !al16(out)) return CPLXAMD_EALIGN;
+  if (n == 0) return 0;
   return launch_ew<3>(x, nullptr, out, n, CPLXAMD_F32, out_dtype, (hipStream_t)stream);
 }
 
 int cplxamd_cast(const void* in, void* out, int64_t n, int in_dtype, int out_dtype,
                  void* stream) {
-  if (!in || !out || n < 0) return CPLXAMD_EINVAL;
+  if (!in || !out || n < 0 || !ew_dtype(in_dtype) || !ew_dtype(out_dtype)) return CPLXAMD_EINVAL;
+  if (!al16(in) || !al16(out)) return CPLXAMD_EALIGN;
+  if (n == 0) return 0;
   return launch_ew<0>(in, nullptr, out, n, in_dtype, out_dtype, (hipStream_t)stream);
 }
 
@@ -457,7 +478,10 @@ int cplxamd_colsum2(const void* in_r, const void* in_i, int64_t ld, float* out_r
 
 int cplxamd_lrt_dx_accum(void* dxr, void* dxi, const void* xr, const void* xi, const void* ga,
                          int64_t n, int dtype, int ga_dtype, void* stream) {
-  if (!dxr || !xr || !ga || n < 0 || ((dxi == nullptr) != (xi == nullptr))) return CPLXAMD_EINVAL;
+  if (!dxr || !xr || !ga || n < 0 || ((dxi == nullptr) != (xi == nullptr)) || !ew_dtype(dtype) || !ew_dtype(ga_dtype))
+    return CPLXAMD_EINVAL;
+  if (!al16(dxr) || !al16(dxi) || !al16(xr) || !al16(xi) || !al16(ga)) return CPLXAMD_EALIGN;
+  if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int grid = stream_grid(n >> 2, kUT);
 #define DX(T, TG)                                                                              \

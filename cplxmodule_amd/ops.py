@@ -73,6 +73,11 @@ def _cf(t, fmt):
     return None if t is None else t.contiguous(memory_format=fmt)
 
 
+def _al16(t):
+    """The streaming kernels move 16 bytes per lane: re-home the rare view that is not aligned."""
+    return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _f32(t):
     if t is not None and t.dtype != torch.float32:
         raise _lib.CplxAmdError(f"expected a float32 tensor, got {t.dtype}")
@@ -87,7 +92,7 @@ def cast(t, dtype):
     if t.dtype == dtype:
         return t
     require_device(t)
-    t = _cf(t, _layout_of(t))             # (elementwise: any one dense layout; a channels-last tensor stays so)
+    t = _al16(_cf(t, _layout_of(t)))      # (elementwise: any one dense layout; a channels-last tensor stays so)
     out = torch.empty_like(t, dtype=dtype)
     call("cplxamd_cast", ptr(t), ptr(out), t.numel(), dtype_code(t), dtype_code(out), stream_ptr())
     return out
@@ -198,7 +203,7 @@ def abs2(xr, xi=None, out_dtype=None):
     """xr^2 + xi^2 (or xr^2), cplxmodule/nn/relevance/complex/base.py:51."""
     require_device(xr, xi)
     fmt = _layout_of(xr)
-    xr, xi = _cf(xr, fmt), _cf(xi, fmt)
+    xr, xi = _al16(_cf(xr, fmt)), _al16(_cf(xi, fmt))
     out = torch.empty_like(xr, dtype=out_dtype or xr.dtype)
     call("cplxamd_abs2", ptr(xr), ptr(xi), ptr(out), xr.numel(), dtype_code(xr),
          dtype_code(out), stream_ptr())
@@ -209,7 +214,7 @@ def modulus(xr, xi):
     """abs(Cplx), cplxmodule/cplx.py:183-192 (float32 or bfloat16 planes)."""
     require_device(xr, xi)
     fmt = _layout_of(xr)
-    xr, xi = _cf(xr, fmt), _cf(xi, fmt)
+    xr, xi = _al16(_cf(xr, fmt)), _al16(_cf(xi, fmt))
     out = torch.empty_like(xr)
     call("cplxamd_cplx_abs_fwd", ptr(xr), ptr(xi), ptr(out), xr.numel(), dtype_code(xr), stream_ptr())
     return out
@@ -218,7 +223,7 @@ def modulus(xr, xi):
 def mask_mul(tr, ti, mask, out_dtype=None):
     """(tr * mask, ti * mask) in one pass, converted to `out_dtype`; ti may be None (real layers)."""
     require_device(tr, ti, mask)
-    tr, ti, mask = _c(tr), _c(ti), _f32(_c(mask.expand_as(tr)))
+    tr, ti, mask = _al16(_c(tr)), _al16(_c(ti)), _al16(_f32(_c(mask.expand_as(tr))))
     odt = out_dtype or tr.dtype
     our = torch.empty_like(tr, dtype=odt)
     oui = None if ti is None else torch.empty_like(ti, dtype=odt)
@@ -229,7 +234,7 @@ def mask_mul(tr, ti, mask, out_dtype=None):
 
 def exp(x, out_dtype=torch.float32):
     require_device(x)
-    x = _f32(_c(x))
+    x = _al16(_f32(_c(x)))
     out = torch.empty_like(x, dtype=out_dtype)
     call("cplxamd_exp", ptr(x), ptr(out), x.numel(), dtype_code(out), stream_ptr())
     return out
@@ -400,11 +405,6 @@ def philox_advance(state):
     return used
 
 
-def _al16(t):
-    """The streaming kernels move 16 bytes per lane: re-home the rare view that is not aligned."""
-    return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
-
-
 def _s2(s2, like):
     """The variance operand of the noise injection: float32, or bf16 as the variance GEMM / convolution of a bf16
     layer wrote it (kept as it is: no float32 copy of a [B, O] tensor)."""
@@ -501,8 +501,14 @@ def reparam_bwd(g_r, g_i, s2, eps=None, seed=0, offset=0, out_dtype=torch.float3
 
 def lrt_dx_accum(dxr, dxi, xr, xi, ga):
     require_device(dxr, dxi, xr, xi, ga)
-    call("cplxamd_lrt_dx_accum", ptr(dxr), ptr(dxi), ptr(xr), ptr(xi), ptr(ga), dxr.numel(),
+    ar, ai = _al16(dxr), _al16(dxi)      # accumulated in place: a re-homed plane is copied back
+    xr, xi, ga = _al16(xr), _al16(xi), _al16(ga)
+    call("cplxamd_lrt_dx_accum", ptr(ar), ptr(ai), ptr(xr), ptr(xi), ptr(ga), dxr.numel(),
          dtype_code(dxr), dtype_code(ga), stream_ptr())
+    if ar is not dxr:
+        dxr.copy_(ar)
+    if ai is not dxi:
+        dxi.copy_(ai)
 
 
 def kl_fwd(kind, wr, wi, ls2, elementwise=False, total=True):
@@ -1494,6 +1500,7 @@ class AbsFn(torch.autograd.Function):
         g = _cf(g, ctx.fmt)
         if g.dtype != zr.dtype:
             g = cast(g, zr.dtype)
+        g, zr, zi = _al16(g), _al16(zr), _al16(zi)
         dzr, dzi = torch.empty_like(zr), torch.empty_like(zi)
         call("cplxamd_cplx_abs_bwd", ptr(g), ptr(zr), ptr(zi), ptr(dzr), ptr(dzi), zr.numel(),
              dtype_code(zr), stream_ptr())
@@ -1663,6 +1670,8 @@ def _tau_args(tau, like, fmt=torch.contiguous_format):
     t = _f32(tau)
     if t.numel() == 1:
         return t, 0.0, 1, t
+    if like.numel() == 0:                # nothing to threshold: no tensor goes to the kernel (it takes 0, 1 or n elements)
+        return None, 0.0, 0, None
     t = _al16(t.expand(like.shape).contiguous(memory_format=fmt))
     return t, 0.0, t.numel(), t
 

@@ -387,6 +387,11 @@ int cplxamd_rgemm_ex(const void* a, int64_t a_rs, int64_t a_cs, const void* b, i
 
 /* ------------------------------------------------------------------------------------
  * elementwise / layout helpers used by the layers (all HBM-bound streaming kernels)
+ *
+ * cplxamd_abs2, _modulus, _cplx_abs_fwd, _cplx_abs_bwd, _mask_mul, _exp, _cast and (further down) _lrt_dx_accum move
+ * 16 bytes per lane: every plane pointer, the mask included, must be 16-byte aligned, whatever the dtype.  A pointer
+ * that is not returns CPLXAMD_EALIGN before anything is launched (after the CPLXAMD_EINVAL checks: NULL, n < 0, a
+ * dtype other than F32 / BF16); n == 0 returns 0 without a launch.
  * ---------------------------------------------------------------------------------- */
 /* out = xr^2 + xi^2 (xi NULL: xr^2)            nn/relevance/complex/base.py:51 */
 int cplxamd_abs2(const void* xr, const void* xi, void* out, int64_t n, int in_dtype,
@@ -516,7 +521,8 @@ int cplxamd_colsum(const void* in, int64_t ld, float* out, int rows, int cols, i
  * cplxamd_colsum's few-rows path, else two cplxamd_colsum passes.  ws as for cplxamd_colsum. */
 int cplxamd_colsum2(const void* in_r, const void* in_i, int64_t ld, float* out_r, float* out_i, int rows, int cols,
                     int dtype, void* ws, void* stream);
-/* dxr += 2 xr ga ; dxi += 2 xi ga   (LRT backward; xi/dxi NULL for real) */
+/* dxr += 2 xr ga ; dxi += 2 xi ga   (LRT backward; xi/dxi NULL for real); planes 16-byte aligned
+ * (CPLXAMD_EALIGN), as for the elementwise helpers above */
 int cplxamd_lrt_dx_accum(void* dxr, void* dxi, const void* xr, const void* xi, const void* ga,
                          int64_t n, int dtype, int ga_dtype, void* stream);
 
