@@ -209,6 +209,12 @@ SIGNATURES = {
     # still ABI 25: the real-input / real-output transforms behind cplx.rfft / irfft / hfft / ihfft (csrc/rfft.hip)
     "cplxamd_rfft_plan": [_L, _L, _I, _I, _P, _P, _P, _P],
     "cplxamd_rfft": [_P, _P, _P, _P, _P, _I, _I, _P, _L, _P],
+    # still ABI 25: the short-time transforms behind cplx.stft / istft (csrc/stft.hip; the descriptor is StftDesc)
+    "cplxamd_stft_plan": [_L, _L, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "cplxamd_stft_src": [_P, _L, _L],
+    "cplxamd_stft_fold": [_P, _L, _P],
+    "cplxamd_stft": [_P, _P, _P, _P, _I, _P, _L, _P],
+    "cplxamd_istft": [_P, _P, _P, _P, _I, _P, _L, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -228,9 +234,18 @@ class FftDesc(ctypes.Structure):
                 ("scale", c_double)]
 
 
+class StftDesc(ctypes.Structure):
+    """cplxamd_stft_desc: framing (n_fft, hop, frames), the signal (length, pad, pad_mode, strides), the spectrogram
+    strides, one row run, the window, the envelope and the imaginary-plane pointers, flags and scale."""
+    _fields_ = [("n_fft", c_int64), ("hop", c_int64), ("frames", c_int64), ("length", c_int64), ("pad", c_int64),
+                ("rows", c_int64), ("sig_row_stride", c_int64), ("sig_es", c_int64), ("spec_row_stride", c_int64),
+                ("spec_frame_stride", c_int64), ("spec_es", c_int64), ("pad_mode", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("window", c_void_p), ("envelope", c_void_p), ("sig_imag", c_void_p), ("scale", c_double)]
+
+
 # function codes of cplxamd_cplx_fn_fwd / _bwd (CPLXAMD_FN_*)
 CPLX_FN = {"exp": 0, "log": 1, "sin": 2, "cos": 3, "tan": 4, "sinh": 5, "cosh": 6, "tanh": 7}
-_RESTYPES = {"cplxamd_absmax_ws_bytes": c_int64, "cplxamd_init_ws_bytes": c_int64, "cplxamd_conv2d_cl2_mom_chunks": c_int64, "cplxamd_conv2d_cl2_mom_chunks_fl": c_int64, "cplxamd_vd_kl_ws_bytes": c_int64, "cplxamd_lrt_reparam_bwd_cols_ws_bytes": c_int64, "cplxamd_l0_gate_bwd_ws_bytes": c_int64, "cplxamd_bn_ws_bytes": c_int64,
+_RESTYPES = {"cplxamd_stft_src": c_int64, "cplxamd_absmax_ws_bytes": c_int64, "cplxamd_init_ws_bytes": c_int64, "cplxamd_conv2d_cl2_mom_chunks": c_int64, "cplxamd_conv2d_cl2_mom_chunks_fl": c_int64, "cplxamd_vd_kl_ws_bytes": c_int64, "cplxamd_lrt_reparam_bwd_cols_ws_bytes": c_int64, "cplxamd_l0_gate_bwd_ws_bytes": c_int64, "cplxamd_bn_ws_bytes": c_int64,
              "cplxamd_conv2d_wgrad_ws_bytes": c_int64, "cplxamd_conv2d_bf16_wgrad_ws_bytes": c_int64, "cplxamd_colsum_ws_bytes": c_int64, "cplxamd_gemm_ws_bytes": c_int64,
              "cplxamd_cgemm3m_ws_bytes": c_int64,
              "cplxamd_live_index_ws_bytes": c_int64,

@@ -801,6 +801,26 @@ def ihfft(input, n=None, dim=-1, norm=None):
     return Cplx(*_rfft.rfftn(input, _one(n), [dim], norm, True, "ihfft"))
 
 
+def stft(input, n_fft, hop_length=None, win_length=None, window=None, center=True, pad_mode="reflect", normalized=False,
+         onesided=None):
+    r"""Short-time Fourier transform with `torch.stft`'s arguments and shape rules -> `Cplx` [..., N, frames] in torch's
+    memory order, always (there is no `return_complex`).  Framing, reflect / constant padding and the window happen in the
+    kernel's loader: no frame and no padded copy is made.  Any number of leading dims; `window=None` is rectangular.
+    Deterministic, capturable, differentiable to any order (cplxmodule_amd/stft.py)."""
+    from . import stft as _stft
+    return _stft.stft(input, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided)
+
+
+def istft(input, n_fft, hop_length=None, win_length=None, window=None, center=True, normalized=False, onesided=None,
+          length=None, return_complex=False, *, check_nola=True):
+    r"""Inverse of `stft` with `torch.istft`'s arguments: a `Cplx` spectrogram [..., N, frames] -> a real tensor [..., T]
+    (`onesided=False, return_complex=True`: a `Cplx`).  The overlap-add is one gather pass in a fixed order (no atomics).  `check_nola=True` reads the minimum of the window
+    envelope on the host and raises RuntimeError below 1e-11, as torch does; pass False inside a stream capture."""
+    from . import stft as _stft
+    return _stft.istft(input, n_fft, hop_length, win_length, window, center, normalized, onesided, length, return_complex,
+                       check_nola=check_nola)
+
+
 def fftshift(input, dim=None):
     """`torch.fft.fftshift` on each plane (plumbing: any device)."""
     return Cplx(torch.fft.fftshift(input.real, dim=dim), torch.fft.fftshift(input.imag, dim=dim))

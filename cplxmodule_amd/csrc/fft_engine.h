@@ -313,6 +313,12 @@ template <int LOGM> constexpr int kVecs = kPackT / kNT<LOGM>;
 // words of one vector's LDS slice in a packed workgroup: odd
 template <int LOGM> constexpr int kSlice = 2 * (pad(1 << LOGM) + 1) + 1;
 
+// The default loader / store policy of Io (fft_impl.h) and RIo (rfft_impl.h): nothing framed, nothing windowed, no
+// storage.  The short-time transforms (stft_impl.h) bring their own.
+struct NoStft {
+  static constexpr bool kFramed = false, kWindowed = false;
+};
+
 // the batch of a call: three runs (unused ones have size 1), run 2 innermost
 struct Batch {
   int64_t total, s1, s2, xs[3], ys[3];

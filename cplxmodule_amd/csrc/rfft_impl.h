@@ -6,7 +6,11 @@
 namespace cplxamd {
 namespace sp {
 
-template <typename TI, typename TO, typename T>
+// P: the loader / store policy of the short-time transforms (NoStft of fft_engine.h adds nothing):
+//   kFramed    real_in(xo, j) is pol.load(xr, xo, j): xo is a VIRTUAL offset that names row and frame, the policy maps
+//              it (padding index map, window) to a sample or to zero
+//   kWindowed  the real outputs of C2R are multiplied by pol.win(j) in the store
+template <typename TI, typename TO, typename T, typename P = NoStft>
 struct RIo {
   const TI* xr; const TI* xi; TO* yr; TO* yi;             // R2C reads xr alone, C2R writes yr alone
   int64_t xes, yes, n, h, n_in, L;                        // L: points of the complex transform, h (HALF) or n
@@ -15,10 +19,12 @@ struct RIo {
   T sg;
   bool weighted;
   T scale;
+  [[no_unique_address]] P pol;                            // the default takes no storage: the kernel arguments are what they were
 
   __device__ __forceinline__ bool edge(int64_t k) const { return k == 0 || 2 * k == n; }   // DC, Nyquist
   __device__ __forceinline__ T real_in(int64_t xo, int64_t j) const {
-    return j < n_in ? (T)ld<TI>::at(xr + xo + j * xes) : (T)0;
+    if constexpr (P::kFramed) return j < n_in ? pol.load(xr, xo, j) : (T)0;
+    else return j < n_in ? (T)ld<TI>::at(xr + xo + j * xes) : (T)0;
   }
   // c_k X_k / w_k of the half spectrum, k in [0, h]: what the Hermitian extension is formed from
   __device__ __forceinline__ C2<T> half_in(int64_t xo, int64_t k) const {
@@ -63,10 +69,16 @@ struct RIo {
     if constexpr (C2R) {
       const C2<T> y = z(k);
       if constexpr (HALF) {
-        st_t(yr + yo + 2 * k * yes, y.re * scale);
-        st_t(yr + yo + (2 * k + 1) * yes, y.im * scale);
+        if constexpr (P::kWindowed) {
+          st_t(yr + yo + 2 * k * yes, y.re * scale * pol.win(2 * k));
+          st_t(yr + yo + (2 * k + 1) * yes, y.im * scale * pol.win(2 * k + 1));
+        } else {
+          st_t(yr + yo + 2 * k * yes, y.re * scale);
+          st_t(yr + yo + (2 * k + 1) * yes, y.im * scale);
+        }
       } else {
-        st_t(yr + yo + k * yes, y.re * scale);
+        if constexpr (P::kWindowed) st_t(yr + yo + k * yes, y.re * scale * pol.win(k));
+        else st_t(yr + yo + k * yes, y.re * scale);
       }
     } else if constexpr (HALF) {
       const C2<T> a = z(k == h ? 0 : k), b = z(k == 0 || k == h ? 0 : h - k);   // indices mod h
@@ -81,8 +93,8 @@ struct RIo {
 
 // ---- V vectors per workgroup, the complex transform of 2^LOGM points in the vector's LDS slice (fft_lds of fft.hip
 // with the real loaders and stores) -----------------------------------------------------------------------------------
-template <typename TI, typename TO, typename T, bool C2R, bool HALF, bool BLUE, int LOGM, int V, bool STAGED>
-__global__ __launch_bounds__(V * kNT<LOGM>) void rfft_lds(RIo<TI, TO, T> io, Batch b, const C2<T>* tw) {
+template <typename TI, typename TO, typename T, bool C2R, bool HALF, bool BLUE, int LOGM, int V, bool STAGED, typename P = NoStft>
+__global__ __launch_bounds__(V * kNT<LOGM>) void rfft_lds(RIo<TI, TO, T, P> io, Batch b, const C2<T>* tw) {
   static_assert(!STAGED || V > 1, "staging is for packed workgroups");
   constexpr int E = kEOf<LOGM>, M = 1 << LOGM, NT = kNT<LOGM>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -167,8 +179,8 @@ __global__ __launch_bounds__(V * kNT<LOGM>) void rfft_lds(RIo<TI, TO, T> io, Bat
 }
 
 // ---- through the workspace ---------------------------------------------------------------------------------------------
-template <typename TI, typename TO, typename T, bool C2R, bool HALF, bool BLUE>
-__global__ __launch_bounds__(kET) void rfft_gather(RIo<TI, TO, T> io, Batch b, int64_t v0, int64_t nv, int64_t M, C2<T>* buf) {
+template <typename TI, typename TO, typename T, bool C2R, bool HALF, bool BLUE, typename P = NoStft>
+__global__ __launch_bounds__(kET) void rfft_gather(RIo<TI, TO, T, P> io, Batch b, int64_t v0, int64_t nv, int64_t M, C2<T>* buf) {
   for (int64_t i = (int64_t)blockIdx.x * kET + threadIdx.x; i < nv * M; i += (int64_t)gridDim.x * kET) {
     const int64_t v = i / M, p = i % M;
     C2<T> a{0, 0};
@@ -181,8 +193,8 @@ __global__ __launch_bounds__(kET) void rfft_gather(RIo<TI, TO, T> io, Batch b, i
   }
 }
 
-template <typename TI, typename TO, typename T, bool C2R, bool HALF, bool BLUE>
-__global__ __launch_bounds__(kET) void rfft_scatter(RIo<TI, TO, T> io, Batch b, int64_t v0, int64_t nv, int64_t M,
+template <typename TI, typename TO, typename T, bool C2R, bool HALF, bool BLUE, typename P = NoStft>
+__global__ __launch_bounds__(kET) void rfft_scatter(RIo<TI, TO, T, P> io, Batch b, int64_t v0, int64_t nv, int64_t M,
                                                    const C2<T>* buf) {
   const int64_t count = io.template count<C2R>();
   for (int64_t i = (int64_t)blockIdx.x * kET + threadIdx.x; i < nv * count; i += (int64_t)gridDim.x * kET) {
@@ -217,19 +229,19 @@ inline int rfft_plan_for(int64_t n, int64_t vectors, int dtype, RfftPlan& p) {
   return 0;
 }
 
-template <typename TI, typename TO, typename T, bool C2R, bool HALF, bool BLUE, int LOGM, int V, bool STAGED>
-int launch_rlds(const RIo<TI, TO, T>& io, const Batch& b, const C2<T>* tw, hipStream_t st) {
+template <typename TI, typename TO, typename T, bool C2R, bool HALF, bool BLUE, int LOGM, int V, bool STAGED, typename P>
+int launch_rlds(const RIo<TI, TO, T, P>& io, const Batch& b, const C2<T>* tw, hipStream_t st) {
   static PerDeviceOnce once;
-  if (const int e = lds_attr(once, rfft_lds<TI, TO, T, C2R, HALF, BLUE, LOGM, V, STAGED>)) return e;
+  if (const int e = lds_attr(once, rfft_lds<TI, TO, T, C2R, HALF, BLUE, LOGM, V, STAGED, P>)) return e;
   const int64_t wgs = ceil_div(b.total, V);
   const int lds = V == 1 ? lds_bytes<T>(LOGM) : V * kSlice<LOGM> * (int)sizeof(T);
-  rfft_lds<TI, TO, T, C2R, HALF, BLUE, LOGM, V, STAGED><<<(unsigned)wgs, V * kNT<LOGM>, lds, st>>>(io, b, tw);
+  rfft_lds<TI, TO, T, C2R, HALF, BLUE, LOGM, V, STAGED, P><<<(unsigned)wgs, V * kNT<LOGM>, lds, st>>>(io, b, tw);
   CPLXAMD_CHECK_LAUNCH();
   return 0;
 }
 
-template <typename TI, typename TO, typename T, bool C2R, bool HALF, bool BLUE>
-int rfft_run(const FftPlan& p, const RIo<TI, TO, T>& io, const Batch& b, const C2<T>* tw, char* ws, hipStream_t st) {
+template <typename TI, typename TO, typename T, bool C2R, bool HALF, bool BLUE, typename P>
+int rfft_run(const FftPlan& p, const RIo<TI, TO, T, P>& io, const Batch& b, const C2<T>* tw, char* ws, hipStream_t st) {
   constexpr int LO = BLUE ? 3 : 0;                        // a Bluestein M is at least 8
   // a direct transform of an odd length has one point (n = 1)
   constexpr int PACK_HI = !BLUE && !HALF ? 0 : kLogPackMax;
@@ -252,7 +264,7 @@ int rfft_run(const FftPlan& p, const RIo<TI, TO, T>& io, const Batch& b, const C
     const int64_t count = io.template count<C2R>();
     for (int64_t v0 = 0; v0 < b.total; v0 += p.GL) {
       const int64_t nv = b.total - v0 < p.GL ? b.total - v0 : p.GL;
-      rfft_gather<TI, TO, T, C2R, HALF, BLUE><<<ew_grid(nv * p.M), kET, 0, st>>>(io, b, v0, nv, p.M, buf);
+      rfft_gather<TI, TO, T, C2R, HALF, BLUE, P><<<ew_grid(nv * p.M), kET, 0, st>>>(io, b, v0, nv, p.M, buf);
       CPLXAMD_CHECK_LAUNCH();
       if (const int e = fft_vectors<T>(p.logM, tw, buf, tmp, nv, BLUE ? (T)-1 : io.sg, st)) return e;
       if constexpr (BLUE) {
@@ -260,7 +272,7 @@ int rfft_run(const FftPlan& p, const RIo<TI, TO, T>& io, const Batch& b, const C
         CPLXAMD_CHECK_LAUNCH();
         if (const int e = fft_vectors<T>(p.logM, tw, buf, tmp, nv, (T)1, st)) return e;
       }
-      rfft_scatter<TI, TO, T, C2R, HALF, BLUE><<<ew_grid(nv * count), kET, 0, st>>>(io, b, v0, nv, p.M, buf);
+      rfft_scatter<TI, TO, T, C2R, HALF, BLUE, P><<<ew_grid(nv * count), kET, 0, st>>>(io, b, v0, nv, p.M, buf);
       CPLXAMD_CHECK_LAUNCH();
     }
     return 0;
@@ -268,30 +280,31 @@ int rfft_run(const FftPlan& p, const RIo<TI, TO, T>& io, const Batch& b, const C
   return CPLXAMD_EINVAL;
 }
 
-template <typename TI, typename TO, typename T, bool C2R>
+// `build`: write the per-call tables first (false: an earlier call with the same n and dtype left them in ws)
+template <typename TI, typename TO, typename T, bool C2R, typename P = NoStft>
 int rfft_t(const void* xr, const void* xi, void* yr, void* yi, const cplxamd_fft_desc& d, const Batch& b, const RfftPlan& rp,
-           char* ws, hipStream_t st) {
+           char* ws, hipStream_t st, const P& pol = P{}, bool build = true) {
   const FftPlan& p = rp.c;
   C2<T>* tw = (C2<T>*)(ws + p.off_tw);
   C2<T>* chirp = (C2<T>*)(ws + p.off_chirp);
   C2<T>* bhat = (C2<T>*)(ws + p.off_bhat);
   C2<T>* rt = (C2<T>*)(ws + rp.off_rt);
-  if (p.blue || p.logM > 3) {                             // up to 8 points: one register stage, no twiddle is read
+  if (build && (p.blue || p.logM > 3)) {                  // up to 8 points: one register stage, no twiddle is read
     tables<T><<<ew_grid(p.M), kET, 0, st>>>(tw, p.M, p.blue ? chirp : nullptr, rp.L);
     CPLXAMD_CHECK_LAUNCH();
   }
-  if (rp.half) {
+  if (build && rp.half) {
     rfft_twiddles<T><<<ew_grid(rp.L), kET, 0, st>>>(rt, rp.L, d.n);
     CPLXAMD_CHECK_LAUNCH();
   }
-  if (p.blue) {
+  if (build && p.blue) {
     chirp_filter<T><<<ew_grid(p.M), kET, 0, st>>>(bhat, rp.L, p.M);
     CPLXAMD_CHECK_LAUNCH();
     if (const int e = fft_vectors<T>(p.logM, tw, bhat, (C2<T>*)(ws + p.off_buf), 1, (T)-1, st)) return e;
   }
-  const RIo<TI, TO, T> io{(const TI*)xr, (const TI*)xi, (TO*)yr, (TO*)yi, d.x_es, d.y_es, d.n, d.n / 2, d.n_in, rp.L, chirp,
+  const RIo<TI, TO, T, P> io{(const TI*)xr, (const TI*)xi, (TO*)yr, (TO*)yi, d.x_es, d.y_es, d.n, d.n / 2, d.n_in, rp.L, chirp,
                           bhat, rt, (d.inverse & CPLXAMD_FFT_INVERSE) ? (T)1 : (T)-1, (d.inverse & CPLXAMD_RFFT_WEIGHTED) != 0,
-                          (T)d.scale};
+                          (T)d.scale, pol};
   if (rp.half)
     return p.blue ? rfft_run<TI, TO, T, C2R, true, true>(p, io, b, tw, ws, st)
                   : rfft_run<TI, TO, T, C2R, true, false>(p, io, b, tw, ws, st);

@@ -1031,6 +1031,72 @@ int cplxamd_rfft(const void* x_r, const void* x_i, void* y_r, void* y_i, const c
                  int in_dtype, int out_dtype, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Short-time Fourier transforms (cplx.stft / istft; csrc/stft.hip on the kernels of cplxamd_rfft and cplxamd_fft).  New
+ * exports under ABI 25: nothing existing changes.  With N = n_fft / 2 + 1, the sign and w_k / c_k of cplxamd_rfft
+ * (CPLXAMD_FFT_INVERSE, CPLXAMD_RFFT_WEIGHTED in `flags`), a window `win` of n_fft values and P = length + 2 pad:
+ *   cplxamd_stft   S[row][f][k] = scale [w_k] sum_{j < n_fft} win[j] x[row][src(f hop + j)] e^{-+ 2 pi i jk/n_fft},
+ *                  row < rows, f < frames, k < N.  src(q) is the sample index of position q of the virtually padded
+ *                  signal, or "zero" (the term is dropped, nothing is loaded): outside [0, P) zero; with i = q - pad,
+ *                  CPLXAMD_STFT_PAD_ZERO gives i when 0 <= i < length, else zero; CPLXAMD_STFT_PAD_REFLECT (pad < length)
+ *                  gives -i for i < 0 and 2 (length - 1) - i for i >= length.  Sample i of a row lies at
+ *                  x[row sig_row_stride + i sig_es] (strides >= 0), S at y_r / y_i [row spec_row_stride + f
+ *                  spec_frame_stride + k spec_es] (strides >= 1; outputs must not alias).  One launch of the R2C kernels
+ *                  with the frame axis as the innermost batch run: no frame and no padded copy is materialised.
+ *   cplxamd_istft  y[row][t] = e[t] sum_{p in fold(t)} sum_{f ascending, 0 <= p - f hop < n_fft} F[row][f][p - f hop],
+ *                  t < length, with F[row][f][j] = win[j] scale Re sum_{k < N} c_k X[row][f][k] e^{-+ 2 pi i jk/n_fft} held in
+ *                  the workspace in the compute type, and fold(t) the positions q with src(q) = t, ascending: pad + t, and
+ *                  for _REFLECT also pad - t (1 <= t <= pad) and pad + 2 (length - 1) - t (length - 1 - pad <= t <=
+ *                  length - 2).  X is read at x_r / x_i with the spec strides (>= 0), y written with the sig strides
+ *                  (sig_es >= 1), rounded once.  `envelope` NULL: e = 1 (the adjoint of cplxamd_stft with the same
+ *                  fields).  Otherwise it points to length + 1 values of the compute type that the call WRITES: e[t] = 1 /
+ *                  env[t], env[t] = sum_{f ascending} win^2[t + pad - f hop] (e = 0 where no frame covers t + pad), and
+ *                  at [length] the minimum of |env| over the covered t (untouched when there is none).
+ * CPLXAMD_STFT_FULL in `flags` selects the full spectrum on the kernels of cplxamd_fft: N = n_fft, x = x_re + i x_im with
+ * x_im the plane `sig_imag` (same strides as x; NULL: a plane of zeros that is never read), no w_k (CPLXAMD_RFFT_WEIGHTED
+ * is an error); in cplxamd_istft c_k = 1, F is complex (no Re; two planes of frames in the workspace), y receives the real
+ * part and `sig_imag` the imaginary part (NULL: it is not written).  Without the flag `sig_imag` must be NULL.
+ * dtype (of x, S, X and y alike): F32, BF16 (float32 arithmetic, window, frames and envelope) or F64; `window` and
+ * `envelope` have the compute type.  No atomics and fixed summation orders: the same input gives the same bits.
+ * cplxamd_stft_plan is a pure function: frames = 1 + (padded_length - n_fft) / hop, the path (return value), the complex
+ * length, the points and the vectors per workgroup of the underlying transform (as cplxamd_rfft_plan for rows x frames
+ * vectors; `full` nonzero: as cplxamd_fft_plan of n_fft points), the rows one synthesis chunk holds (frames of a chunk stay within 256 MiB; one row may exceed it) and the
+ * workspace bytes of each direction for signals / outputs of `length` samples (nullable outputs); CPLXAMD_EINVAL for
+ * out-of-range arguments.  cplxamd_stft_src / _fold are the index maps, compiled from the code the kernels use, for
+ * host-side proofs of the addresses: the sample index of (frame, j), -1 for "zero", -2 for arguments out of range; and
+ * the number of fold positions of t written to positions[0 .. 2] (CPLXAMD_EINVAL out of range).  The launchers check every
+ * argument before any launch: CPLXAMD_EINVAL (NULL, dtype, any field out of range, unknown flag bits, a scale that is not
+ * finite, an envelope given to cplxamd_stft), CPLXAMD_ESHAPE (more than 2^31 - 1 frames in all, or offsets beyond 64
+ * bits), CPLXAMD_EWS.  Zero rows (and for cplxamd_stft zero frames): no launch, returns 0.
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_STFT_PAD_ZERO = 0, CPLXAMD_STFT_PAD_REFLECT = 1 };
+enum { CPLXAMD_STFT_FULL = 16 };                 /* full spectrum of a complex signal (default: one-sided, real signal)     */
+typedef struct cplxamd_stft_desc {
+  int64_t n_fft;             /* frame and transform length, 1 .. 2^22 */
+  int64_t hop;               /* >= 1 */
+  int64_t frames;            /* per row, >= 0 */
+  int64_t length;            /* samples per row: read by cplxamd_stft, written by cplxamd_istft; >= 1 */
+  int64_t pad;               /* virtual samples in front of sample 0 (and behind the last), 0 .. 2^22 */
+  int64_t rows;
+  int64_t sig_row_stride, sig_es;                        /* the signal, in elements */
+  int64_t spec_row_stride, spec_frame_stride, spec_es;   /* the spectrogram planes, in elements */
+  int32_t pad_mode;          /* CPLXAMD_STFT_PAD_* */
+  int32_t flags;             /* CPLXAMD_FFT_INVERSE | CPLXAMD_RFFT_WEIGHTED | CPLXAMD_STFT_FULL */
+  const void* window;        /* n_fft values of the compute type */
+  void* envelope;            /* cplxamd_istft only, see above; NULL: e = 1 */
+  void* sig_imag;            /* CPLXAMD_STFT_FULL only: the signal's imaginary plane (read by cplxamd_stft), or NULL */
+  double scale;
+} cplxamd_stft_desc;         /* 128 bytes */
+int cplxamd_stft_plan(int64_t n_fft, int64_t hop, int64_t padded_length, int64_t rows, int64_t length, int dtype, int full,
+                      int64_t* complex_n, int64_t* points, int* vectors_per_workgroup, int64_t* frames,
+                      int64_t* rows_per_chunk, int64_t* analysis_ws_bytes, int64_t* synthesis_ws_bytes);
+int64_t cplxamd_stft_src(const cplxamd_stft_desc* d, int64_t frame, int64_t j);
+int cplxamd_stft_fold(const cplxamd_stft_desc* d, int64_t t, int64_t* positions);
+int cplxamd_stft(const void* x, void* y_r, void* y_i, const cplxamd_stft_desc* d, int dtype, void* ws, int64_t ws_bytes,
+                 void* stream);
+int cplxamd_istft(const void* x_r, const void* x_i, void* y, const cplxamd_stft_desc* d, int dtype, void* ws,
+                  int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Strided complex tensor contraction (cplx.einsum with two operands, cplxmodule/cplx.py:1032-1059; csrc/einsum.hip).  A new
  * export under ABI 25: nothing existing changes.
  *   C[b.., m.., n..] = sum_{k..} op(A)[b.., m.., k..] * op(B)[b.., n.., k..],   op = identity or conjugate per operand
