@@ -215,6 +215,11 @@ SIGNATURES = {
     "cplxamd_stft_fold": [_P, _L, _P],
     "cplxamd_stft": [_P, _P, _P, _P, _I, _P, _L, _P],
     "cplxamd_istft": [_P, _P, _P, _P, _I, _P, _L, _P],
+    # still ABI 25: overlap-save convolution behind cplx.fftconvolve (csrc/fftconv.hip, fftconv_wgrad.hip; the descriptor
+    # is FftConvDesc, the plan fills FFTCONV_PLAN_FIELDS int64)
+    "cplxamd_fftconv_plan": [_L, _L, _L, _L, _L, _L, _I, _I, _I, _P],
+    "cplxamd_fftconv": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P],
+    "cplxamd_fftconv_wgrad": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -241,6 +246,20 @@ class StftDesc(ctypes.Structure):
                 ("rows", c_int64), ("sig_row_stride", c_int64), ("sig_es", c_int64), ("spec_row_stride", c_int64),
                 ("spec_frame_stride", c_int64), ("spec_es", c_int64), ("pad_mode", ctypes.c_int32), ("flags", ctypes.c_int32),
                 ("window", c_void_p), ("envelope", c_void_p), ("sig_imag", c_void_p), ("scale", c_double)]
+
+
+class FftConvDesc(ctypes.Structure):
+    """cplxamd_fftconv_desc: lengths (a, taps, result / second operand), the window's start, element strides, up to
+    three batch runs (run 0 outermost), the correlation flag and the block-length override."""
+    _fields_ = [("a_len", c_int64), ("k", c_int64), ("c_len", c_int64), ("start", c_int64), ("a_es", c_int64),
+                ("b_es", c_int64), ("runs", ctypes.c_int32), ("conj", ctypes.c_int32), ("log_l", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("size", c_int64 * 3), ("a_stride", c_int64 * 3), ("b_stride", c_int64 * 3),
+                ("y_stride", c_int64 * 3)]
+
+
+# fields of cplxamd_fftconv_plan's output (CPLXAMD_FFTCONV_*)
+FFTCONV_PLAN_FIELDS = ("log_l", "S", "blocks", "vectors_per_workgroup", "in_shift", "out_lo", "n_valid", "ws_bytes",
+                       "wgrad_log_l", "wgrad_S", "wgrad_blocks", "wgrad_chunks", "wgrad_per_chunk", "wgrad_ws_bytes")
 
 
 # function codes of cplxamd_cplx_fn_fwd / _bwd (CPLXAMD_FN_*)

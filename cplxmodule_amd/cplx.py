@@ -821,6 +821,21 @@ def istft(input, n_fft, hop_length=None, win_length=None, window=None, center=Tr
                        check_nola=check_nola)
 
 
+def fftconvolve(input, other, mode="full"):
+    r"""Linear convolution along the last dim, full[n] = sum_m input[n - m] other[m] (a plain complex product, nothing
+    is conjugated), with the modes of `scipy.signal.fftconvolve` / `torchaudio.functional.fftconvolve`: "full" returns
+    all N + M - 1 entries, "same" full[(M - 1) // 2 : (M - 1) // 2 + N] (the length of `input`, whichever operand is
+    longer), "valid" full[min(N, M) - 1 : max(N, M)].  Each operand is a `Cplx` or a real tensor (a null imaginary
+    plane: no zero plane is built); two real operands give a real tensor, else a `Cplx`, dense, in the operands' dtype
+    (float32, bfloat16 -- float32 arithmetic, rounded once -- or float64, on the device).  Leading dims broadcast by
+    torch's rules and are read in place (step slices, `expand`, transposed leading dims: no copy).  The shorter operand
+    is the filter: up to 4096 taps one fused overlap-save kernel reads the long operand once and writes the result once
+    (csrc/fftconv.hip); longer filters are composed from cplx.fft launches.  Deterministic, capturable in a hipGraph,
+    differentiable to any order (cplxmodule_amd/fftconv.py)."""
+    from . import fftconv as _fftconv
+    return _fftconv.fftconvolve(input, other, mode)
+
+
 def fftshift(input, dim=None):
     """`torch.fft.fftshift` on each plane (plumbing: any device)."""
     return Cplx(torch.fft.fftshift(input.real, dim=dim), torch.fft.fftshift(input.imag, dim=dim))

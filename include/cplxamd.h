@@ -1097,6 +1097,76 @@ int cplxamd_istft(const void* x_r, const void* x_i, void* y, const cplxamd_stft_
                   int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Linear convolution and correlation along the last dim by overlap-save on the FFT engine (cplx.fftconvolve;
+ * csrc/fftconv.hip, fftconv_wgrad.hip).  New exports under ABI 25: nothing existing changes.  Two primitives over rows
+ * r = (i0, i1, i2) of up to three batch runs (run 0 outermost), with a[.] = 0 outside [0, a_len):
+ *   cplxamd_fftconv        y[r][n] = sum_{m < k} a[r][n + start - m] b[r][m]              (conj = 0: convolution)
+ *                          y[r][n] = sum_{m < k} a[r][n + start + m] conj(b[r][m])        (conj = 1: correlation)
+ *                          for n in [0, c_len).  b is the filter: a run whose b stride is 0 shares one filter, and one
+ *                          spectrum H-hat = FFT_L(b zero-padded to L) / L is built per DISTINCT filter (the product of
+ *                          the sizes of the runs with a non-zero b stride) in the workspace, by the packed transform
+ *                          kernel of cplxamd_fft with n_in = k.  One launch then runs, per block of L = 2^log_l points,
+ *                          load -> FFT -> times H-hat (or its conjugate) -> inverse FFT -> store inside one workgroup;
+ *                          y is written once, rounded once.  start and start + c_len may lie anywhere (zeros result
+ *                          where no product exists).
+ *   cplxamd_fftconv_wgrad  y[f][m] = sum_{rows of f} sum_{n < a_len} conj(a[r][n]) b[r][n + m + start],  m in [0, k),
+ *                          with b[.] = 0 outside [0, c_len).  A run whose y stride is 0 is REDUCED: its rows are summed
+ *                          into one result.  Per (result, chunk) one workgroup accumulates conj(A-hat) B-hat over its
+ *                          chunk of (reduced row, block) pairs in ascending order in registers and writes one partial
+ *                          spectrum to the workspace; the partials of a result are summed in ascending chunk order (one
+ *                          thread per entry), then one inverse transform keeps k taps (scale 1 / L, one rounding).  No
+ *                          atomics.  It has its own block length (the plan's WGRAD fields).
+ * Element j of row r of operand t lies at t_r / t_i [sum_q i_q t_stride[q] + j t_es] (y: element stride 1).  a_i, b_i and
+ * y_i may each be NULL: a NULL input plane is a plane of zeros that is never read, a NULL y_i is not written (the real
+ * part alone is wanted).  dtype (of every plane): F32, BF16 (widened on load, float32 arithmetic and spectra, rounded once
+ * on store) or F64.  Each is the other's gradient, so derivatives of every order stay on these two.
+ * cplxamd_fftconv_plan is a pure function (no GPU).  It fills out[CPLXAMD_FFTCONV_PLAN_FIELDS] (see the enum) for
+ * operands of a_len and k entries, the window (start, c_len), `rows` rows, `filters` distinct filters / results and
+ * `conj`; log_l = 0 asks for the plan's own L, a value in [1, 13] with 2^log_l >= k forces it (measurements, exact tests).
+ * Returns CPLXAMD_FFTCONV_FUSED, or CPLXAMD_FFTCONV_COMPOSED for k > 4096 (the caller composes cplxamd_fft launches of
+ * 2^out[CPLXAMD_FFTCONV_LOG_L] >= a_len + k - 1 points; above 2^22: CPLXAMD_ESHAPE), or CPLXAMD_ESHAPE (fused: filter spectra
+ * or one partial spectrum per result beyond 1 TiB, pair counts beyond 64 bits), or CPLXAMD_EINVAL (sizes < 1 -- rows and
+ * filters < 0 --, a bad dtype, 2^log_l < k, log_l > 13).  Block j of a row loads a[j S + in_shift + i], i < L, and stores
+ * entry i of the cyclic result to y[j S + ((i - out_lo) mod L)] where that index is below min(n_valid, c_len - j S).
+ * The launchers run the same plan and check before any launch: CPLXAMD_EINVAL (NULL a_r / b_r / y_r / d / ws, dtype, a
+ * field out of range, a composed length), CPLXAMD_ESHAPE (more than 2^31 - 1 blocks), CPLXAMD_EWS.  No rows: returns 0.
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_FFTCONV_FUSED = 0, CPLXAMD_FFTCONV_COMPOSED = 1 };
+enum { CPLXAMD_FFTCONV_LOG_L = 0,        /* L = 2^this (COMPOSED: of the composed transform length)                    */
+       CPLXAMD_FFTCONV_S,                /* outputs per block = the block stride along a row                           */
+       CPLXAMD_FFTCONV_BLOCKS,           /* blocks per row                                                             */
+       CPLXAMD_FFTCONV_VPW,              /* blocks per workgroup: 2048 / L up to L = 1024 (256 below 8), else 1        */
+       CPLXAMD_FFTCONV_IN_SHIFT,         /* see above                                                                  */
+       CPLXAMD_FFTCONV_OUT_LO,
+       CPLXAMD_FFTCONV_N_VALID,
+       CPLXAMD_FFTCONV_WS_BYTES,         /* of cplxamd_fftconv                                                         */
+       CPLXAMD_FFTCONV_WGRAD_LOG_L,      /* the same for cplxamd_fftconv_wgrad: its own L, S, blocks per row of a,     */
+       CPLXAMD_FFTCONV_WGRAD_S,
+       CPLXAMD_FFTCONV_WGRAD_BLOCKS,
+       CPLXAMD_FFTCONV_WGRAD_CHUNKS,     /* chunks per result, pairs per chunk                                         */
+       CPLXAMD_FFTCONV_WGRAD_PER_CHUNK,
+       CPLXAMD_FFTCONV_WGRAD_WS_BYTES,
+       CPLXAMD_FFTCONV_PLAN_FIELDS };
+typedef struct cplxamd_fftconv_desc {
+  int64_t a_len;        /* entries of a row of a, >= 1 */
+  int64_t k;            /* filter taps: entries of b (cplxamd_fftconv) or of y (cplxamd_fftconv_wgrad), >= 1 */
+  int64_t c_len;        /* entries of y (cplxamd_fftconv) or of b (cplxamd_fftconv_wgrad), >= 1 */
+  int64_t start;        /* any sign */
+  int64_t a_es, b_es;   /* element strides along the last dim, >= 0 */
+  int32_t runs;         /* 0 .. 3 batch runs, run 0 outermost */
+  int32_t conj;         /* cplxamd_fftconv: 0 convolution, 1 correlation; cplxamd_fftconv_wgrad: 0 */
+  int32_t log_l;        /* 0: the plan's choice; else L = 2^log_l >= k, log_l <= 13 */
+  int32_t reserved;     /* 0 */
+  int64_t size[3], a_stride[3], b_stride[3], y_stride[3];
+} cplxamd_fftconv_desc; /* 160 bytes */
+int cplxamd_fftconv_plan(int64_t a_len, int64_t k, int64_t start, int64_t c_len, int64_t rows, int64_t filters, int dtype,
+                         int conj, int log_l, int64_t* out);
+int cplxamd_fftconv(const void* a_r, const void* a_i, const void* b_r, const void* b_i, void* y_r, void* y_i,
+                    const cplxamd_fftconv_desc* d, int dtype, void* ws, int64_t ws_bytes, void* stream);
+int cplxamd_fftconv_wgrad(const void* a_r, const void* a_i, const void* b_r, const void* b_i, void* y_r, void* y_i,
+                          const cplxamd_fftconv_desc* d, int dtype, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Strided complex tensor contraction (cplx.einsum with two operands, cplxmodule/cplx.py:1032-1059; csrc/einsum.hip).  A new
  * export under ABI 25: nothing existing changes.
  *   C[b.., m.., n..] = sum_{k..} op(A)[b.., m.., k..] * op(B)[b.., n.., k..],   op = identity or conjugate per operand
