@@ -220,6 +220,11 @@ SIGNATURES = {
     "cplxamd_fftconv_plan": [_L, _L, _L, _L, _L, _L, _I, _I, _I, _P],
     "cplxamd_fftconv": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P],
     "cplxamd_fftconv_wgrad": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P],
+    # still ABI 25: the polyphase rate change behind cplx.upfirdn / resample_poly (csrc/upfirdn.hip, upfirdn_wgrad.hip; the
+    # descriptor is UpfirdnDesc, the plan fills UPFIRDN_PLAN_FIELDS int64)
+    "cplxamd_upfirdn_plan": [_L, _L, _L, _L, _L, _L, _L, _L, _I, _I, _I, _I, _P],
+    "cplxamd_upfirdn": [_P, _P, _P, _P, _P, _P, _P, _I, _P],
+    "cplxamd_upfirdn_wgrad": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -260,6 +265,20 @@ class FftConvDesc(ctypes.Structure):
 # fields of cplxamd_fftconv_plan's output (CPLXAMD_FFTCONV_*)
 FFTCONV_PLAN_FIELDS = ("log_l", "S", "blocks", "vectors_per_workgroup", "in_shift", "out_lo", "n_valid", "ws_bytes",
                        "wgrad_log_l", "wgrad_S", "wgrad_blocks", "wgrad_chunks", "wgrad_per_chunk", "wgrad_ws_bytes")
+
+
+class UpfirdnDesc(ctypes.Structure):
+    """cplxamd_upfirdn_desc: lengths (a, taps, result / second operand), the rates and the offset, element strides, up
+    to three batch runs (run 0 outermost) and the correlation flag."""
+    _fields_ = [("a_len", c_int64), ("k", c_int64), ("c_len", c_int64), ("up", c_int64), ("down", c_int64), ("off", c_int64),
+                ("a_es", c_int64), ("b_es", c_int64), ("runs", ctypes.c_int32), ("conj", ctypes.c_int32),
+                ("size", c_int64 * 3), ("a_stride", c_int64 * 3), ("b_stride", c_int64 * 3), ("y_stride", c_int64 * 3)]
+
+
+# fields of cplxamd_upfirdn_plan's output (CPLXAMD_UPFIRDN_*)
+UPFIRDN_PLAN_FIELDS = ("T", "tiles", "vectors_per_workgroup", "span", "phases", "jseg", "segs", "lds_bytes", "threads", "grid",
+                       "wgrad_Tn", "wgrad_tiles", "wgrad_kb", "wgrad_kblocks", "wgrad_span", "wgrad_lds_bytes",
+                       "wgrad_chunks", "wgrad_per_chunk", "wgrad_ws_bytes")
 
 
 # function codes of cplxamd_cplx_fn_fwd / _bwd (CPLXAMD_FN_*)

@@ -836,6 +836,35 @@ def fftconvolve(input, other, mode="full"):
     return _fftconv.fftconvolve(input, other, mode)
 
 
+def upfirdn(h, x, up=1, down=1):
+    r"""Upsample by `up`, FIR filter, downsample by `down` along the last dim, with the argument order and the result of
+    `scipy.signal.upfirdn` (`mode="constant"`): y[n] = sum_k h[k] xu[n down - k] where xu[i up] = x[i] and zero
+    elsewhere, for n < ceil(((N - 1) up + K) / down).  `h` and `x` are each a `Cplx` or a real tensor (a null imaginary
+    plane: no zero plane is built); two real operands give a real tensor, else a `Cplx`, dense, in the operands' dtype
+    (float32, bfloat16 -- float32 arithmetic, rounded once -- or float64, on the device).  Leading dims of `x` and `h`
+    broadcast by torch's rules (a filter per channel, or one for all) and are read in place (step slices, `expand`,
+    transposed leading dims: no copy).  Up to 4096 taps one direct-form polyphase kernel (csrc/upfirdn.hip) reads the
+    signal once and writes the result once: xu is never built and each output costs ceil(K / up) multiply-adds.  Longer
+    filters are composed from torch zero-stuffing, cplx.fftconvolve and a strided slice, which is not the hot path.
+    Deterministic, capturable in a hipGraph, differentiable to any order in both operands (cplxmodule_amd/upfirdn.py).
+    There is no `axis`: move the dim."""
+    from . import upfirdn as _upfirdn
+    return _upfirdn.upfirdn(h, x, up, down)
+
+
+def resample_poly(x, up, down, window=("kaiser", 5.0)):
+    r"""Resample along the last dim by the rational factor up / down with a polyphase low-pass, as
+    `scipy.signal.resample_poly` does with `padtype="constant"`: ceil(N up / down) entries.  `up` and `down` are reduced
+    by their gcd; equal rates return a copy of the input.  `window` is `("kaiser", beta)`: a Kaiser-windowed sinc of
+    20 max(up, down) + 1 taps with its cut-off at 1 / max(up, down) of Nyquist and gain `up`, designed in float64 on the
+    host with torch and cached (a constant: it has no gradient); or a 1-d real tensor of taps, which is the filter (times
+    `up`, as scipy scales the array it is given) and receives a gradient if it requires one.  The whole resampling is one
+    launch of cplx.upfirdn's kernel with the filter's delay folded into its offset: nothing is padded, nothing is sliced.
+    `x` is a `Cplx` or a real tensor; dtypes, broadcasting, layouts and derivatives as `upfirdn`."""
+    from . import upfirdn as _upfirdn
+    return _upfirdn.resample_poly(x, up, down, window)
+
+
 def fftshift(input, dim=None):
     """`torch.fft.fftshift` on each plane (plumbing: any device)."""
     return Cplx(torch.fft.fftshift(input.real, dim=dim), torch.fft.fftshift(input.imag, dim=dim))

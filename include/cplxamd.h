@@ -1167,6 +1167,76 @@ int cplxamd_fftconv_wgrad(const void* a_r, const void* a_i, const void* b_r, con
                           const cplxamd_fftconv_desc* d, int dtype, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Rational rate change along the last dim on direct-form polyphase kernels (cplx.upfirdn, cplx.resample_poly;
+ * csrc/upfirdn.hip, upfirdn_wgrad.hip).  New exports under ABI 25: nothing existing changes.  Write au for a row of a
+ * upsampled by `up`: au[i up] = a[i], zero elsewhere and outside the row (never materialised).  Two primitives over rows
+ * r = (i0, i1, i2) of up to three batch runs (run 0 outermost):
+ *   cplxamd_upfirdn        y[r][n] = sum_{m < k} b[r][m] au[r][n down + off - m]             (conj = 0: convolution)
+ *                          y[r][n] = sum_{m < k} conj(b[r][m]) au[r][n down + off + m]       (conj = 1: correlation)
+ *                          for n in [0, c_len).  b is the filter (k <= 4096 taps); a run whose b stride is 0 shares one.
+ *                          A workgroup takes `vpw` tiles of T consecutive outputs, stages the samples of a the tiles
+ *                          touch (zeros outside the row) and the filter in polyphase-major order into LDS, and spends
+ *                          ceil(k / up) complex multiply-adds per output: structural zeros are never multiplied.  When
+ *                          the filter and the span exceed the LDS budget the taps are walked in `segs` segments of
+ *                          `jseg` taps per phase, in ascending order, the sums staying in registers (the same bits).
+ *   cplxamd_upfirdn_wgrad  y[f][m] = sum_{rows of f} sum_{n < c_len} conj(au[r][n down + off - m]) b[r][n],  m in [0, k).
+ *                          A run whose y stride is 0 is REDUCED.  Workgroup (result, chunk, block of <= 1024 taps) walks
+ *                          its chunk of (reduced row, tile of Tn entries of b) pairs in ascending order, one thread per
+ *                          tap, and writes a partial to the workspace; a finishing kernel adds the partials of a result
+ *                          in ascending chunk order and rounds once.  No atomics: reruns give the same bits.
+ * Element j of row r of operand t lies at t_r / t_i [sum_q i_q t_stride[q] + j t_es] (y: element stride 1).  a_i, b_i and
+ * y_i may each be NULL: a NULL input plane is a plane of zeros that is never read (the kernels are compiled per real /
+ * complex operand pair), a NULL y_i is not written.  dtype (of every plane): F32, BF16 (float32 arithmetic, rounded
+ * once on store) or F64.  Each is the other's gradient with up and down swapped.
+ * cplxamd_upfirdn_plan is a pure function (no GPU).  It fills out[CPLXAMD_UPFIRDN_PLAN_FIELDS] (see the enum) for rows of
+ * a_len entries, k taps, c_len results (wgrad: entries of b), the rates, `rows` rows, `filters` distinct filters / results
+ * and the kinds of the operands (a_cplx, b_cplx: 0 real, 1 complex).  Returns CPLXAMD_UPFIRDN_FUSED, or
+ * CPLXAMD_UPFIRDN_COMPOSED for k > 4096 (the caller composes cplxamd_fftconv), or CPLXAMD_EINVAL (sizes, up or down < 1,
+ * rows or filters < 0, a bad dtype or flag), or CPLXAMD_ESHAPE (up or down above 2^30, lengths above 2^40, |off| above 2^48,
+ * more than 2^31 - 1 workgroups, partials beyond 1 TiB).
+ * The launchers run the same plan and check before any launch: CPLXAMD_EINVAL (NULL a_r / b_r / y_r / d, a NULL ws of
+ * cplxamd_upfirdn_wgrad, dtype, a field out of range, a composed length), CPLXAMD_ESHAPE, CPLXAMD_EWS.  No rows: returns 0.
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_UPFIRDN_FUSED = 0, CPLXAMD_UPFIRDN_COMPOSED = 1 };
+enum { CPLXAMD_UPFIRDN_T = 0,            /* outputs per tile                                                            */
+       CPLXAMD_UPFIRDN_TILES,            /* tiles per row                                                               */
+       CPLXAMD_UPFIRDN_VPW,              /* tiles per workgroup (> 1 only when a row is one tile)                       */
+       CPLXAMD_UPFIRDN_SPAN,             /* staged samples of a per tile and segment                                    */
+       CPLXAMD_UPFIRDN_PHASES,           /* staged phases: min(up, k)                                                   */
+       CPLXAMD_UPFIRDN_JSEG,             /* taps per phase and segment; ceil(k / up) when the filter is staged whole    */
+       CPLXAMD_UPFIRDN_SEGS,             /* segments                                                                    */
+       CPLXAMD_UPFIRDN_LDS_BYTES,
+       CPLXAMD_UPFIRDN_THREADS,
+       CPLXAMD_UPFIRDN_GRID,
+       CPLXAMD_UPFIRDN_WGRAD_TN,         /* cplxamd_upfirdn_wgrad: entries of b per tile, tiles per row,                */
+       CPLXAMD_UPFIRDN_WGRAD_TILES,
+       CPLXAMD_UPFIRDN_WGRAD_KB,         /* taps per workgroup, blocks of taps                                          */
+       CPLXAMD_UPFIRDN_WGRAD_KBLOCKS,
+       CPLXAMD_UPFIRDN_WGRAD_SPAN,       /* staged samples of a per tile                                                */
+       CPLXAMD_UPFIRDN_WGRAD_LDS_BYTES,
+       CPLXAMD_UPFIRDN_WGRAD_CHUNKS,     /* chunks per result, pairs per chunk                                          */
+       CPLXAMD_UPFIRDN_WGRAD_PER_CHUNK,
+       CPLXAMD_UPFIRDN_WGRAD_WS_BYTES,
+       CPLXAMD_UPFIRDN_PLAN_FIELDS };
+typedef struct cplxamd_upfirdn_desc {
+  int64_t a_len;        /* entries of a row of a, >= 1 */
+  int64_t k;            /* filter taps: entries of b (cplxamd_upfirdn) or of y (cplxamd_upfirdn_wgrad), >= 1 */
+  int64_t c_len;        /* entries of y (cplxamd_upfirdn) or of b (cplxamd_upfirdn_wgrad), >= 1 */
+  int64_t up, down;     /* >= 1 */
+  int64_t off;          /* any sign */
+  int64_t a_es, b_es;   /* element strides along the last dim, >= 0 */
+  int32_t runs;         /* 0 .. 3 batch runs, run 0 outermost */
+  int32_t conj;         /* cplxamd_upfirdn: 0 convolution, 1 correlation; cplxamd_upfirdn_wgrad: 0 */
+  int64_t size[3], a_stride[3], b_stride[3], y_stride[3];
+} cplxamd_upfirdn_desc; /* 168 bytes */
+int cplxamd_upfirdn_plan(int64_t a_len, int64_t k, int64_t c_len, int64_t up, int64_t down, int64_t off, int64_t rows,
+                         int64_t filters, int dtype, int conj, int a_cplx, int b_cplx, int64_t* out);
+int cplxamd_upfirdn(const void* a_r, const void* a_i, const void* b_r, const void* b_i, void* y_r, void* y_i,
+                    const cplxamd_upfirdn_desc* d, int dtype, void* stream);
+int cplxamd_upfirdn_wgrad(const void* a_r, const void* a_i, const void* b_r, const void* b_i, void* y_r, void* y_i,
+                          const cplxamd_upfirdn_desc* d, int dtype, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Strided complex tensor contraction (cplx.einsum with two operands, cplxmodule/cplx.py:1032-1059; csrc/einsum.hip).  A new
  * export under ABI 25: nothing existing changes.
  *   C[b.., m.., n..] = sum_{k..} op(A)[b.., m.., k..] * op(B)[b.., n.., k..],   op = identity or conjugate per operand
