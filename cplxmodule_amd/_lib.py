@@ -225,6 +225,11 @@ SIGNATURES = {
     "cplxamd_upfirdn_plan": [_L, _L, _L, _L, _L, _L, _L, _L, _I, _I, _I, _I, _P],
     "cplxamd_upfirdn": [_P, _P, _P, _P, _P, _P, _P, _I, _P],
     "cplxamd_upfirdn_wgrad": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P],
+    # still ABI 25: the chunk-parallel recurrence behind cplx.lfilter / sosfilt (csrc/iir.hip; the descriptor is IirDesc,
+    # the plan fills IIR_PLAN_FIELDS int64)
+    "cplxamd_iir_plan": [_L, _L, _L, _L, _L, _I, _I, _L, _P],
+    "cplxamd_iir": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "cplxamd_iir_scan": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _I, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -279,6 +284,20 @@ class UpfirdnDesc(ctypes.Structure):
 UPFIRDN_PLAN_FIELDS = ("T", "tiles", "vectors_per_workgroup", "span", "phases", "jseg", "segs", "lds_bytes", "threads", "grid",
                        "wgrad_Tn", "wgrad_tiles", "wgrad_kb", "wgrad_kblocks", "wgrad_span", "wgrad_lds_bytes",
                        "wgrad_chunks", "wgrad_per_chunk", "wgrad_ws_bytes")
+
+
+class IirDesc(ctypes.Structure):
+    """cplxamd_iir_desc: samples per row, states per section, sections, the cut into segments, x's element stride, up to
+    three batch runs (run 0 outermost) and the reverse / conj flags."""
+    _fields_ = [("n", c_int64), ("order", c_int64), ("sections", c_int64), ("segments", c_int64), ("seg_len", c_int64),
+                ("x_es", c_int64), ("runs", ctypes.c_int32), ("flags", ctypes.c_int32), ("size", c_int64 * 3),
+                ("x_stride", c_int64 * 3), ("c_stride", c_int64 * 3), ("y_stride", c_int64 * 3)]
+
+
+# fields of cplxamd_iir_plan's output (CPLXAMD_IIR_*)
+IIR_PLAN_FIELDS = ("chunk", "lanes", "tile", "tiles", "segments", "seg_len", "bucket", "lds_bytes", "threads", "grid",
+                   "ws_bytes")
+IIR_REVERSE, IIR_CONJ = 1, 2
 
 
 # function codes of cplxamd_cplx_fn_fwd / _bwd (CPLXAMD_FN_*)

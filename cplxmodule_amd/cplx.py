@@ -865,6 +865,40 @@ def resample_poly(x, up, down, window=("kaiser", 5.0)):
     return _upfirdn.resample_poly(x, up, down, window)
 
 
+def lfilter(b, a, x, zi=None):
+    r"""Filter along the last dim with the rational transfer function b / a, with the argument order and the result of
+    `scipy.signal.lfilter` (direct form II transposed): a[0] y[n] = sum_k b[k] x[n - k] - sum_{k >= 1} a[k] y[n - k].
+    `b` [..., nb], `a` [..., na], `x` [..., N] and `zi` are each a `Cplx` or a real tensor (a null imaginary plane: no
+    zero plane is built); all-real operands give a real tensor, else a `Cplx`, dense, in the operands' dtype (float32,
+    bfloat16 -- float32 arithmetic and state, rounded once -- or float64, on the device).  Leading dims broadcast by
+    torch's rules (a filter per channel, or one for all) and are read in place (step slices, `expand`, transposed leading
+    dims: no copy).  `a[..., 0]` normalises both `b` and `a` by a differentiable division.  Returns `y`; with `zi`
+    [..., D], D = max(na, nb) - 1, returns `(y, zf)`, the state that continues the filter on the next block.  D = 0 is a
+    scale.  Up to order 8 one chunk-parallel kernel (csrc/iir.hip) reads the signal once and writes the result once; the
+    recurrence is parallel in time inside a tile, and long rows with few rows are cut into segments.  nb - 1 > 8 is
+    composed from one cplx.upfirdn launch and the all-pole kernel; na - 1 > 8 raises `CplxAmdError`: use `sosfilt`.
+    Deterministic, capturable in a hipGraph, differentiable to any order in b, a, x and zi (cplxmodule_amd/iir.py).
+    Unlike scipy: `a[..., 0] == 0` is not checked (that would read the device; it gives inf / nan), and there is no
+    `axis`: move the dim."""
+    from . import iir as _iir
+    return _iir.lfilter(b, a, x, zi)
+
+
+def sosfilt(sos, x, zi=None):
+    r"""Filter along the last dim with a cascade of second-order sections, as `scipy.signal.sosfilt`: `sos`
+    [..., n_sections, 6] holds b0 b1 b2 a0 a1 a2 per section, a `Cplx` or a real tensor; `x`, dtypes, broadcasting,
+    layouts and the result as `lfilter`.  Returns `y`, or `(y, zf)` when `zi` [..., n_sections, 2] is given.  The whole
+    cascade runs inside one launch of `lfilter`'s kernel, a section reading the one before it from on-chip memory (up to
+    16 sections per launch, longer cascades are chained); its gradient with respect to `x` is one launch too, reversed in
+    time, conjugated, sections in reverse order.  When `sos` or `zi` requires a gradient (or `x` does and `zi` is given)
+    the cascade is composed from one differentiable `lfilter` section per biquad, which is not the hot path.
+    Unlike scipy: every section is normalised by its own a0, and `sos[..., 3] != 1` or `== 0` is not checked (a zero gives
+    inf / nan); `zi` keeps n_sections next to the state dim, [..., n_sections, 2], so that leading dims broadcast (scipy
+    puts n_sections first); there is no `axis`."""
+    from . import iir as _iir
+    return _iir.sosfilt(sos, x, zi)
+
+
 def fftshift(input, dim=None):
     """`torch.fft.fftshift` on each plane (plumbing: any device)."""
     return Cplx(torch.fft.fftshift(input.real, dim=dim), torch.fft.fftshift(input.imag, dim=dim))

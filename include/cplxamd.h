@@ -1237,6 +1237,80 @@ int cplxamd_upfirdn_wgrad(const void* a_r, const void* a_i, const void* b_r, con
                           const cplxamd_upfirdn_desc* d, int dtype, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Recursive (IIR) filtering along the last dim on a chunk-parallel kernel (cplx.lfilter, cplx.sosfilt; csrc/iir.hip).
+ * New exports under ABI 25: nothing existing changes.  One primitive over rows r = (i0, i1, i2) of up to three batch runs
+ * (run 0 outermost), each row cut into `segments` segments of seg_len samples (the last one shorter):
+ *   for every (row, segment): take the entering state zi[r][seg] (zeros when zi_r is NULL), run the cascade of
+ *   `sections` direct-form-II-transposed sections of order `order` over the segment's samples in order, carrying one
+ *   state per section, store y (unless y_r is NULL) and the final state zf[r][seg] (unless zf_r is NULL).
+ *     section:  y[n] = b0 x[n] + z0,   z_i = b_{i+1} x[n] - a_{i+1} y[n] + z_{i+1}  (i < order, z_order = 0)
+ *   CPLXAMD_IIR_REVERSE runs the recurrence from the last sample of the row to the first (segment 0 is then the END of
+ *   the row), CPLXAMD_IIR_CONJ conjugates the coefficients.  x_r NULL is a null input (zeros that are never read).
+ * The coefficients of row r lie at c_r / c_i [sum_q i_q c_stride[q]] as [sections][2 (order + 1)] dense entries, section s
+ * holding b0 .. b_order, a0 .. a_order; a0 is NOT read (the caller normalises: it counts as 1).  A run whose c stride is 0
+ * shares one filter.  Sample j of row r of x lies at x_r / x_i [sum_q i_q x_stride[q] + j x_es]; y likewise with element
+ * stride 1.  zi and zf are dense [rows][segments][sections][order] planes, rows in run order.
+ * `cplx` = 0: real arithmetic, every imaginary pointer must be NULL.  `cplx` = 1: complex arithmetic; x_i, c_i, zi_i may
+ * each be NULL (a plane of zeros that is never read), y_i / zf_i must be given where y_r / zf_r are.
+ * dtype (of every plane): F32, BF16 (float32 arithmetic and state, rounded once on store) or F64.
+ * Order: 1 .. 8 with one section, 1 .. 2 with 2 .. 16 sections (kernels are compiled for 2 and 8 states and the
+ * coefficients zero-padded).  Section s + 1 reads section s's tile from LDS; x is read once and y written once.
+ * Inside a tile of LANES * CHUNK samples (a workgroup is one wave, a lane per chunk) each lane runs one chunk of CHUNK
+ * samples from zero state, the chunk-final states are combined across the lanes IN ORDER with the CHUNK-step transition
+ * M = A^CHUNK (P_c = M P_{c-1} + s_c; only M is ever applied, so integer operands stay exact as long as the sequential
+ * recurrence's values times CHUNK + 1 fit the mantissa), and every chunk is corrected by the zero-input response of its
+ * entering state; the tables (`order` zero-input responses of CHUNK samples, M) are rebuilt in LDS by every workgroup,
+ * nothing is kept in the library.  No workgroup waits for another, no atomics: reruns give the same bits.
+ * cplxamd_iir_plan is a pure function (no GPU): fills out[CPLXAMD_IIR_PLAN_FIELDS] for rows of n samples;
+ * force_segments > 0 cuts every row into that many segments (at most n), 0 lets the plan choose.  Returns
+ * CPLXAMD_IIR_ROW (one segment) or CPLXAMD_IIR_SPLIT, or CPLXAMD_EINVAL / CPLXAMD_ESHAPE (n above 2^40, order or sections
+ * out of range, more than 2^31 - 1 workgroups).
+ * cplxamd_iir checks before any launch: CPLXAMD_EINVAL (NULL c_r / d, neither y_r nor zf_r, a plane that `cplx`
+ * forbids or a missing one, dtype, a field out of range, seg_len * segments < n), CPLXAMD_ESHAPE.  No rows: returns 0.
+ * The state planes zi and zf are in the COMPUTE type whatever the dtype: float32 for F32 and BF16, float64 for F64.
+ * cplxamd_iir_scan is the split path's hand-off between launches: for every row, sequentially over its segments,
+ *   e[r][0] = zi[r] (or zeros),  e[r][k + 1] = M[r / rows_per_filter] e[r][k] + z[r][k],   k + 1 < segments
+ * with z [rows][segments][w] the segment-final states from zero entering state (one cplxamd_iir launch with zi NULL
+ * and y NULL), M [filters][w][w] the transition of a full segment stored as M[f][j][i] = component i of the final state
+ * from the unit entering state e_j (one cplxamd_iir launch of `filters * w` rows of seg_len null samples), w =
+ * sections * order, and rows_per_filter consecutive rows sharing a filter; it writes the entering states
+ * e [rows][segments][w], which a last cplxamd_iir launch takes as zi.  One thread per row, fixed order, compute-type
+ * planes (dtype F32 or F64); m_i, zi_i NULL are planes of zeros, cplx = 0 forbids every imaginary pointer.
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_IIR_ROW = 0, CPLXAMD_IIR_SPLIT = 1 };
+enum { CPLXAMD_IIR_REVERSE = 1, CPLXAMD_IIR_CONJ = 2 };
+enum { CPLXAMD_IIR_CHUNK = 0,            /* samples per lane                                                            */
+       CPLXAMD_IIR_LANES,                /* chunks per tile                                                             */
+       CPLXAMD_IIR_TILE,                 /* samples per tile: CHUNK * LANES                                             */
+       CPLXAMD_IIR_TILES,                /* tiles per segment                                                           */
+       CPLXAMD_IIR_SEGMENTS,
+       CPLXAMD_IIR_SEG_LEN,
+       CPLXAMD_IIR_BUCKET,               /* compiled states per section: 2 or 8                                         */
+       CPLXAMD_IIR_LDS_BYTES,
+       CPLXAMD_IIR_THREADS,
+       CPLXAMD_IIR_GRID,                 /* rows * segments                                                             */
+       CPLXAMD_IIR_WS_BYTES,             /* split path: z, M and e of cplxamd_iir_scan for `filters` filters            */
+       CPLXAMD_IIR_PLAN_FIELDS };
+typedef struct cplxamd_iir_desc {
+  int64_t n;            /* samples per row, >= 1 */
+  int64_t order;        /* states per section */
+  int64_t sections;     /* >= 1 */
+  int64_t segments;     /* >= 1 */
+  int64_t seg_len;      /* >= 1, seg_len * segments >= n > seg_len * (segments - 1) */
+  int64_t x_es;         /* element stride of x along the last dim, >= 0 */
+  int32_t runs;         /* 0 .. 3 batch runs, run 0 outermost */
+  int32_t flags;        /* CPLXAMD_IIR_REVERSE | CPLXAMD_IIR_CONJ */
+  int64_t size[3], x_stride[3], c_stride[3], y_stride[3];
+} cplxamd_iir_desc; /* 152 bytes */
+int cplxamd_iir_plan(int64_t n, int64_t order, int64_t sections, int64_t rows, int64_t filters, int dtype, int cplx,
+                     int64_t force_segments, int64_t* out);
+int cplxamd_iir(const void* x_r, const void* x_i, const void* c_r, const void* c_i, const void* zi_r, const void* zi_i,
+                void* y_r, void* y_i, void* zf_r, void* zf_i, const cplxamd_iir_desc* d, int cplx, int dtype, void* stream);
+int cplxamd_iir_scan(const void* z_r, const void* z_i, const void* m_r, const void* m_i, const void* zi_r,
+                     const void* zi_i, void* e_r, void* e_i, int64_t rows, int64_t rows_per_filter, int64_t segments,
+                     int64_t width, int cplx, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Strided complex tensor contraction (cplx.einsum with two operands, cplxmodule/cplx.py:1032-1059; csrc/einsum.hip).  A new
  * export under ABI 25: nothing existing changes.
  *   C[b.., m.., n..] = sum_{k..} op(A)[b.., m.., k..] * op(B)[b.., n.., k..],   op = identity or conjugate per operand
