@@ -230,6 +230,11 @@ SIGNATURES = {
     "cplxamd_iir_plan": [_L, _L, _L, _L, _L, _I, _I, _L, _P],
     "cplxamd_iir": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "cplxamd_iir_scan": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _I, _P],
+    # still ABI 25: the extended pass of that recurrence behind cplx.filtfilt / sosfiltfilt (csrc/filtfilt.hip; the
+    # descriptor is FiltFiltDesc, the plan fills FILTFILT_PLAN_FIELDS int64, _src is the pure index map of the extension)
+    "cplxamd_filtfilt_plan": [_L, _L, _L, _L, _L, _L, _I, _I, _L, _P],
+    "cplxamd_filtfilt_src": [_L, _L, _L, _I, _P],
+    "cplxamd_filtfilt_pass": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -298,6 +303,23 @@ class IirDesc(ctypes.Structure):
 IIR_PLAN_FIELDS = ("chunk", "lanes", "tile", "tiles", "segments", "seg_len", "bucket", "lds_bytes", "threads", "grid",
                    "ws_bytes")
 IIR_REVERSE, IIR_CONJ = 1, 2
+
+
+class FiltFiltDesc(ctypes.Structure):
+    """cplxamd_filtfilt_desc: samples per row of x, the extension on each side, the window of logical samples that is
+    stored, the cascade and the cut into segments of the extended row, x's element stride, up to three batch runs (run 0
+    outermost; z_stride finds the unit state of a row's filter), the reverse / scale flags and the extension mode."""
+    _fields_ = [("n", c_int64), ("edge", c_int64), ("y_lo", c_int64), ("y_n", c_int64), ("order", c_int64),
+                ("sections", c_int64), ("segments", c_int64), ("seg_len", c_int64), ("x_es", c_int64),
+                ("runs", ctypes.c_int32), ("flags", ctypes.c_int32), ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("size", c_int64 * 3), ("x_stride", c_int64 * 3), ("c_stride", c_int64 * 3), ("z_stride", c_int64 * 3),
+                ("y_stride", c_int64 * 3)]
+
+
+# fields of cplxamd_filtfilt_plan's output (CPLXAMD_IIR_*, then CPLXAMD_FILTFILT_LEN, _SIGNAL_BYTES)
+FILTFILT_PLAN_FIELDS = IIR_PLAN_FIELDS + ("ext_len", "signal_bytes")
+FILTFILT_MODES = {"odd": 0, "even": 1, "constant": 2}    # CPLXAMD_FILTFILT_ODD / _EVEN / _CONSTANT
+FILTFILT_REVERSE, FILTFILT_SCALE = 1, 2
 
 
 # function codes of cplxamd_cplx_fn_fwd / _bwd (CPLXAMD_FN_*)

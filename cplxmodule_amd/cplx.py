@@ -899,6 +899,62 @@ def sosfilt(sos, x, zi=None):
     return _iir.sosfilt(sos, x, zi)
 
 
+def lfilter_zi(b, a):
+    r"""The initial state of `lfilter` that is the steady state of the unit step, as `scipy.signal.lfilter_zi`: `b`
+    [..., nb], `a` [..., na] (each a `Cplx` or a real tensor, leading dims broadcast) -> [..., D], D = max(na, nb) - 1, a
+    real tensor when both are real, else a `Cplx`.  `lfilter(b, a, x, zi=lfilter_zi(b, a) * x[..., :1])` starts without
+    a transient.  Coefficient-sized torch arithmetic in closed form (no linear solve), on any device, differentiable:
+    after normalising by `a[..., 0]`, zi[0] = sum_{k >= 1} (b_k - a_k b_0) / sum_k a_k and
+    zi[k] = (1 + a_1 + .. + a_k) zi[0] - sum_{j = 1 .. k} (b_j - a_j b_0).
+    Unlike scipy: a filter with a pole at 1 (sum_k a_k == 0) is not checked (that would read the device) and gives inf /
+    nan where scipy raises."""
+    from . import filtfilt as _ff
+    return _ff.lfilter_zi(b, a)
+
+
+def sosfilt_zi(sos):
+    r"""The initial state of `sosfilt` that is the steady state of the unit step, as `scipy.signal.sosfilt_zi`: `sos`
+    [..., n_sections, 6] (a `Cplx` or a real tensor) -> [..., n_sections, 2], the layout `sosfilt` takes for `zi`.  Section
+    s holds `lfilter_zi` of its biquad times the DC gains sum b / sum a of the sections before it.  Torch arithmetic on
+    any device, differentiable; the remarks of `lfilter_zi` apply."""
+    from . import filtfilt as _ff
+    return _ff.sosfilt_zi(sos)
+
+
+def filtfilt(b, a, x, padtype="odd", padlen=None):
+    r"""Zero-phase filtering along the last dim: the filter b / a forward, then backward, as `scipy.signal.filtfilt` with
+    `method="pad"`.  `x` [..., N] is extended by `padlen` samples on each side (default 3 max(na, nb)): `padtype` "odd"
+    (2 x[0] - x[e - m] on the left), "even" (x[e - m]), "constant" (x[0]) or None (no extension); the right side mirrors
+    the left.  The forward pass runs over the extension from the state `lfilter_zi(b, a) * ext[0]`, the backward pass
+    over the reversed result from `lfilter_zi(b, a) *` (its first sample); the result is reversed and the extension
+    dropped.  Nothing is conjugated.  Operands, dtypes (float32; bfloat16 with float32 arithmetic and a float32
+    intermediate, rounded once; float64), broadcasting of leading dims, in-place reading of sliced / `expand`ed /
+    transposed operands, real or `Cplx` results and the error types are `lfilter`'s.  For 1 <= D <= 8 and no operand
+    requiring grad the call is two launches of `lfilter`'s kernel (csrc/filtfilt.hip): the first forms the extension from
+    `x` where it lies and writes one compute-type workspace of N + 2 padlen samples, the second reads it in reverse and
+    writes the N interior samples; both scale the steady state inside the kernel.  No padded copy, no flip, no slice;
+    deterministic, capturable in a hipGraph.  When an operand requires grad, or D = 0, or nb - 1 > 8, the result is
+    composed from a torch extension, two `lfilter` calls with `zi` and flips (differentiable to any order in b, a and x;
+    not the hot path).  na - 1 > 8 raises `CplxAmdError`: use `sosfiltfilt`.  `ValueError` for an unknown `padtype`, a
+    negative `padlen` and N <= padlen (scipy's wording), raised before the device is looked at.
+    Unlike scipy: there is no `axis` (move the dim), no `method="gust"` and no `irlen`; an empty signal gives an empty
+    result; `a[..., 0] == 0` and sum_k a_k == 0 are not checked (inf / nan)."""
+    from . import filtfilt as _ff
+    return _ff.filtfilt(b, a, x, padtype, padlen)
+
+
+def sosfiltfilt(sos, x, padtype="odd", padlen=None):
+    r"""Zero-phase filtering along the last dim with a cascade of second-order sections, as `scipy.signal.sosfiltfilt`:
+    `filtfilt` with `sosfilt_zi(sos)` for the entering states; `sos`, `x`, dtypes, broadcasting and layouts as `sosfilt`,
+    `padtype` / `padlen` and the errors as `filtfilt`.  Up to 16 sections and no operand requiring grad: two launches,
+    the cascade running inside each.  More sections, or an operand that requires grad: composed from a torch extension, two
+    `sosfilt` calls with `zi` and flips (not the hot path).
+    Unlike scipy: `padlen` defaults to 3 (2 n_sections + 1); scipy subtracts min(#(b2 == 0), #(a2 == 0)) from the bracket,
+    which would read the device here -- pass `padlen` for scipy's number.  No `axis`; the remarks of `sosfilt` apply."""
+    from . import filtfilt as _ff
+    return _ff.sosfiltfilt(sos, x, padtype, padlen)
+
+
 def fftshift(input, dim=None):
     """`torch.fft.fftshift` on each plane (plumbing: any device)."""
     return Cplx(torch.fft.fftshift(input.real, dim=dim), torch.fft.fftshift(input.imag, dim=dim))

@@ -71,14 +71,34 @@ inline int iir_plan_for(int64_t n, int64_t order, int64_t sections, int64_t rows
   return 0;
 }
 
-template <typename TI, typename T>
+// TO, TC: the element types of y and of the coefficients (the extended pass of filtfilt.hip: they differ from x's)
+template <typename TI, typename T, typename TO = TI, typename TC = TI>
 struct IirIo {
-  const TI* xr; const TI* xi; const TI* cr; const TI* ci; const T* zr; const T* zi; TI* yr; TI* yi; T* fr; T* fi;
+  const TI* xr; const TI* xi; const TC* cr; const TC* ci; const T* zr; const T* zi; TO* yr; TO* yi; T* fr; T* fi;
   int64_t n, segs, seg_len, x_es;
-  Sub xy, c;                                              // (x, y) strides; c.p: the coefficients'
+  Sub xy, c;                                              // (x, y) strides; c.p: the coefficients', c.q: the unit state's
   int D, S;
   bool rev, conj;
+  // the extended pass only (EXT): the row has n + 2 edge logical samples, [y_lo, y_lo + y_n) of them are stored
+  int64_t edge, y_lo, y_n;
+  int mode;
+  bool scale;
 };
+
+// ---- the edge extension's index map: the same code on the host (cplxamd_filtfilt_src, the host tests) and in the kernel
+// Logical sample m of a row of n samples extended by e < n samples on each side is
+//   k < 0: x[j];   j < 0: x[k];   else 2 x[k] - x[j]
+// with k an anchor (0 or n - 1).  ODD: the row reflected through its end points, EVEN: mirrored about them, CONSTANT:
+// the end points repeated.  m outside [0, n + 2 e): j = k = -1.
+struct IirSrc { int64_t j, k; };
+__host__ __device__ __forceinline__ IirSrc iir_ext_src(int64_t m, int64_t n, int64_t e, int mode) {
+  if (m < 0 || m >= n + 2 * e) return {-1, -1};
+  const int64_t i = m - e;
+  if (i >= 0 && i < n) return {i, -1};
+  const int64_t k = i < 0 ? 0 : n - 1, j = i < 0 ? -i : 2 * (n - 1) - i;
+  if (mode == CPLXAMD_FILTFILT_CONSTANT) return {-1, k};
+  return {j, mode == CPLXAMD_FILTFILT_ODD ? k : -1};
+}
 
 // lane `lane`'s value in every lane (lane is uniform; every lane of the wave is active)
 __device__ __forceinline__ float wave_bcast(float v, int lane) {
@@ -114,30 +134,58 @@ __device__ __forceinline__ void iir_msub(T& re, T& im, T ar, T ai, T br, T bi) {
 // LDS, per plane (im follows re at a distance of `plane` words): the tile at i + (i >> kLog) (one word per chunk: lanes
 // step L + 1 words, no two lanes of the wave share a bank), the lanes' states [d][lane], the carried states [s][d], then
 // per section the coefficients b0..b_DK a0..a_DK, the zero-input responses [d][j] and M = A^L [i][k].
-template <typename TI, typename T, bool CX, int DK>
-__global__ __launch_bounds__(kIirLanes) void iir_chunks(IirIo<TI, T> g) {
+// EXT (filtfilt.hip) adds, as compile-time policy of the one body: the loader that forms the edge extension from x where it
+// lies (the two anchors x[0], x[n - 1] are fetched once per workgroup into two words per plane behind the tables), the
+// entering state as a unit state [S][D] per filter times the first sample in processing order, and the windowed store.
+template <typename TI, typename T, bool CX, int DK, typename TO = TI, typename TC = TI, bool EXT = false>
+__global__ __launch_bounds__(kIirLanes) void iir_chunks(IirIo<TI, T, TO, TC> g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int kLog = IirChunk<T>::kLog, L = 1 << kLog, TL = L * kIirLanes;
   constexpr int kCo = 2 * (DK + 1), kTab = kCo + DK * L + DK * DK;
   const int tid = threadIdx.x, S = g.S, D = g.D;
-  const int plane = TL + kIirLanes + 1 + DK * kIirLanes + S * DK + S * kTab;
+  const int plane = TL + kIirLanes + 1 + DK * kIirLanes + S * DK + S * kTab + (EXT ? 2 : 0);
   T* tile = (T*)smem;
   T* st = tile + TL + kIirLanes + 1;
   T* carry = st + DK * kIirLanes;
   T* tab = carry + S * DK;
   auto IM = [&](T* p) { return p + plane; };
   const int64_t row = blockIdx.x / g.segs, seg = blockIdx.x - row * g.segs;
-  int64_t xo, yo, co, unused;
+  int64_t xo, yo, co, zo;
   sub_offsets(g.xy, row, xo, yo);
-  sub_offsets(g.c, row, co, unused);
+  sub_offsets(g.c, row, co, zo);
+  const int64_t nlog = EXT ? g.n + 2 * g.edge : g.n;      // samples of the row as the recurrence sees it
+  T* anc = tab + S * kTab;                                // EXT: x[0], x[n - 1]
+  // EXT: logical sample m through the index map (after the barrier that publishes the anchors)
+  auto ext_at = [&](int64_t m, T& re, T& im) {
+    const IirSrc s = iir_ext_src(m, g.n, g.edge, g.mode);
+    T vr = 0, vi = 0;
+    if (s.j >= 0) {
+      vr = g.xr ? (T)ld<TI>::at(g.xr + xo + s.j * g.x_es) : (T)0;
+      if constexpr (CX) vi = g.xi ? (T)ld<TI>::at(g.xi + xo + s.j * g.x_es) : (T)0;
+    }
+    if (s.k >= 0) {
+      const int w = s.k != 0;
+      const T ar = anc[w], ai = CX ? *IM(anc + w) : (T)0;
+      vr = s.j >= 0 ? 2 * ar - vr : ar;
+      vi = s.j >= 0 ? 2 * ai - vi : ai;
+    }
+    re = vr, im = vi;
+  };
+  if constexpr (EXT) {
+    if (tid < 2) {
+      const int64_t at = xo + (tid ? g.n - 1 : 0) * g.x_es;
+      anc[tid] = g.xr ? (T)ld<TI>::at(g.xr + at) : (T)0;
+      if constexpr (CX) *IM(anc + tid) = g.xi ? (T)ld<TI>::at(g.xi + at) : (T)0;
+    }
+  }
   // ---- the coefficients, zero-padded to DK states
   for (int e = tid; e < S * kCo; e += kIirLanes) {
     const int s = e / kCo, k = e - s * kCo, which = k / (DK + 1), kk = k - which * (DK + 1);
     const bool in = kk <= D;
     const int64_t at = co + (int64_t)s * 2 * (D + 1) + which * (D + 1) + kk;
     T* dst = tab + s * kTab + k;
-    *dst = in ? (T)ld<TI>::at(g.cr + at) : (T)0;
-    if constexpr (CX) *IM(dst) = in && g.ci ? (g.conj ? -(T)ld<TI>::at(g.ci + at) : (T)ld<TI>::at(g.ci + at)) : (T)0;
+    *dst = in ? (T)ld<TC>::at(g.cr + at) : (T)0;
+    if constexpr (CX) *IM(dst) = in && g.ci ? (g.conj ? -(T)ld<TC>::at(g.ci + at) : (T)ld<TC>::at(g.ci + at)) : (T)0;
   }
   __syncthreads();
   // ---- zero-input response j of section s over one chunk; its final state is column j of M
@@ -166,22 +214,41 @@ __global__ __launch_bounds__(kIirLanes) void iir_chunks(IirIo<TI, T> g) {
       if constexpr (CX) *IM(pw + i * DK + j) = zi[i];
     }
     // the carried state of (row, segment)
-    const bool in = j < D && g.zr;
+    const bool has = j < D && g.zr;
+    const bool in = has && !(EXT && g.scale);             // (a scaled state is not laid out per row: see below)
     const int64_t at = ((row * g.segs + seg) * S + s) * D + j;
     carry[tid] = in ? g.zr[at] : (T)0;
     if constexpr (CX) *IM(carry + tid) = in && g.zi ? g.zi[at] : (T)0;
+    if constexpr (EXT) {
+      if (g.scale) {                                      // the unit state of the row's filter times the first sample
+        const int64_t ua = zo + (int64_t)s * D + j;
+        const T ur = has ? g.zr[ua] : (T)0, ui = CX && has && g.zi ? g.zi[ua] : (T)0;
+        T fr, fi, pr = 0, pi = 0;
+        ext_at(g.rev ? nlog - 1 : 0, fr, fi);
+        iir_mac<CX>(pr, pi, ur, ui, fr, fi);
+        carry[tid] = pr;
+        if constexpr (CX) *IM(carry + tid) = pi;
+      }
+    }
   }
   __syncthreads();
   // ---- the segment's tiles, in order
-  const int64_t t_begin = seg * g.seg_len, t_end = t_begin + g.seg_len < g.n ? t_begin + g.seg_len : g.n;
+  const int64_t t_begin = seg * g.seg_len, t_end = t_begin + g.seg_len < nlog ? t_begin + g.seg_len : nlog;
   const int base = tid * (L + 1);                         // tid L + q + ((tid L + q) >> kLog) = base + q for q < L
   for (int64_t t0 = t_begin; t0 < t_end; t0 += TL) {
     const int cnt = t_end - t0 < TL ? (int)(t_end - t0) : TL;
     for (int p = tid; p < cnt; p += kIirLanes) {
-      const int64_t m = g.rev ? g.n - 1 - (t0 + p) : t0 + p;
+      const int64_t m = g.rev ? nlog - 1 - (t0 + p) : t0 + p;
       const int at = p + (p >> kLog);
-      tile[at] = g.xr ? (T)ld<TI>::at(g.xr + xo + m * g.x_es) : (T)0;
-      if constexpr (CX) *IM(tile + at) = g.xi ? (T)ld<TI>::at(g.xi + xo + m * g.x_es) : (T)0;
+      if constexpr (EXT) {
+        T vr, vi;
+        ext_at(m, vr, vi);
+        tile[at] = vr;
+        if constexpr (CX) *IM(tile + at) = vi;
+      } else {
+        tile[at] = g.xr ? (T)ld<TI>::at(g.xr + xo + m * g.x_es) : (T)0;
+        if constexpr (CX) *IM(tile + at) = g.xi ? (T)ld<TI>::at(g.xi + xo + m * g.x_es) : (T)0;
+      }
     }
     __syncthreads();
     const int nl = (cnt + L - 1) >> kLog;                 // lanes with samples
@@ -299,10 +366,16 @@ __global__ __launch_bounds__(kIirLanes) void iir_chunks(IirIo<TI, T> g) {
     }
     if (g.yr) {
       for (int p = tid; p < cnt; p += kIirLanes) {
-        const int64_t m = g.rev ? g.n - 1 - (t0 + p) : t0 + p;
+        const int64_t m = g.rev ? nlog - 1 - (t0 + p) : t0 + p;
         const int at = p + (p >> kLog);
-        st_t(g.yr + yo + m, tile[at]);
-        if constexpr (CX) st_t(g.yi + yo + m, *IM(tile + at));
+        if constexpr (EXT) {
+          if (m < g.y_lo || m >= g.y_lo + g.y_n) continue;   // only the window is kept
+          st_t(g.yr + yo + (m - g.y_lo), tile[at]);
+          if constexpr (CX) st_t(g.yi + yo + (m - g.y_lo), *IM(tile + at));
+        } else {
+          st_t(g.yr + yo + m, tile[at]);
+          if constexpr (CX) st_t(g.yi + yo + m, *IM(tile + at));
+        }
       }
     }
     __syncthreads();

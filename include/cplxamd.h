@@ -1311,6 +1311,55 @@ int cplxamd_iir_scan(const void* z_r, const void* z_i, const void* m_r, const vo
                      int64_t width, int cplx, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Zero-phase filtering (cplx.filtfilt, cplx.sosfiltfilt; csrc/filtfilt.hip): the EXTENDED pass of the recurrence above.
+ * New exports under ABI 25: nothing existing changes, cplxamd_iir and its descriptor are as they were.  The pass is
+ * cplxamd_iir's primitive (same kernel body, same tile / chunk / segment scheme, same rules) with three additions:
+ *   1. the row the recurrence sees has n + 2 edge LOGICAL samples: x extended by `edge` < n samples on each side, formed
+ *      by the loader from x where it lies (no padded copy).  Logical sample m is, by the index map cplxamd_filtfilt_src,
+ *      x[j], x[k] or 2 x[k] - x[j]:   ODD 2 x[0] - x[edge - m] | x[m - edge] | 2 x[n - 1] - x[2 (n - 1) + edge - m],
+ *      EVEN x[edge - m] | .. | x[2 (n - 1) + edge - m],  CONSTANT x[0] | .. | x[n - 1].  edge = 0: the row itself.
+ *   2. CPLXAMD_FILTFILT_SCALE: zi is a UNIT state [sections][order] per filter (found through z_stride, as the
+ *      coefficients are through c_stride) and the entering state of the row is that state times the first logical sample
+ *      in processing order (the last one under CPLXAMD_FILTFILT_REVERSE); a complex product when cplx = 1.  Only with
+ *      segments = 1.  Without the flag zi is cplxamd_iir's dense [rows][segments][sections][order].
+ *   3. only the logical samples [y_lo, y_lo + y_n) are stored, at y[m - y_lo], in out_dtype.
+ * x is read in in_dtype, y written in out_dtype: (F32, F32), (BF16, F32), (F32, BF16) or (F64, F64).  The coefficients
+ * and every state plane are in the compute type (float32; float64 for F64).  Zero-phase filtering is two passes: x ->
+ * a compute-type workspace of n + 2 edge samples (SCALE), then the workspace reversed -> y with the window [edge, edge + n)
+ * (REVERSE | SCALE, edge 0): for bf16 operands the intermediate signal is never rounded to bf16.
+ * cplxamd_filtfilt_plan (pure, no GPU) fills out[CPLXAMD_FILTFILT_PLAN_FIELDS]: cplxamd_iir_plan's fields for rows of
+ * n + 2 edge samples (the LDS bytes with the anchors: two more words per plane), then the extended length and the bytes
+ * of the intermediate workspace; `dtype` is the operands'.  Returns as cplxamd_iir_plan (EINVAL also for edge < 0 or
+ * edge >= n).  cplxamd_filtfilt_src (pure) writes out[0] = j, out[1] = k (-1 where absent) of logical sample m; returns
+ * 0, or EINVAL for m outside [0, n + 2 edge), edge outside [0, n), n < 1 or an unknown mode.
+ * cplxamd_filtfilt_pass checks before any launch as cplxamd_iir does, and: the dtype pair, the mode, 0 <= edge < n,
+ * 0 <= y_lo, 1 <= y_n, y_lo + y_n <= n + 2 edge (when y_r is given), SCALE with zi_r and one segment.
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_FILTFILT_ODD = 0, CPLXAMD_FILTFILT_EVEN = 1, CPLXAMD_FILTFILT_CONSTANT = 2 };
+enum { CPLXAMD_FILTFILT_REVERSE = 1, CPLXAMD_FILTFILT_SCALE = 2 };
+enum { CPLXAMD_FILTFILT_LEN = CPLXAMD_IIR_PLAN_FIELDS,   /* n + 2 edge                                              */
+       CPLXAMD_FILTFILT_SIGNAL_BYTES,                    /* the intermediate: rows (n + 2 edge) compute-type planes */
+       CPLXAMD_FILTFILT_PLAN_FIELDS };
+typedef struct cplxamd_filtfilt_desc {
+  int64_t n;            /* samples per row of x, >= 1 */
+  int64_t edge;         /* extension on each side, 0 <= edge < n */
+  int64_t y_lo, y_n;    /* the logical samples that are stored */
+  int64_t order, sections, segments, seg_len; /* as cplxamd_iir_desc, over the n + 2 edge logical samples */
+  int64_t x_es;         /* element stride of x along the last dim, >= 0 */
+  int32_t runs;         /* 0 .. 3 batch runs, run 0 outermost */
+  int32_t flags;        /* CPLXAMD_FILTFILT_REVERSE | CPLXAMD_FILTFILT_SCALE */
+  int32_t mode;         /* CPLXAMD_FILTFILT_ODD / _EVEN / _CONSTANT */
+  int32_t reserved;     /* 0 */
+  int64_t size[3], x_stride[3], c_stride[3], z_stride[3], y_stride[3];
+} cplxamd_filtfilt_desc; /* 208 bytes */
+int cplxamd_filtfilt_plan(int64_t n, int64_t edge, int64_t order, int64_t sections, int64_t rows, int64_t filters, int dtype,
+                          int cplx, int64_t force_segments, int64_t* out);
+int cplxamd_filtfilt_src(int64_t m, int64_t n, int64_t edge, int mode, int64_t* out);
+int cplxamd_filtfilt_pass(const void* x_r, const void* x_i, const void* c_r, const void* c_i, const void* zi_r,
+                          const void* zi_i, void* y_r, void* y_i, void* zf_r, void* zf_i, const cplxamd_filtfilt_desc* d,
+                          int cplx, int in_dtype, int out_dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Strided complex tensor contraction (cplx.einsum with two operands, cplxmodule/cplx.py:1032-1059; csrc/einsum.hip).  A new
  * export under ABI 25: nothing existing changes.
  *   C[b.., m.., n..] = sum_{k..} op(A)[b.., m.., k..] * op(B)[b.., n.., k..],   op = identity or conjugate per operand
