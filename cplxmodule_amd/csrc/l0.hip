@@ -476,7 +476,11 @@ int cplxamd_l0_gate_bwd(const void* d, const void* a, const float* log_alpha, co
   if (!dt_ok(d_dtype) || !dt_ok(a_dtype) || !dt_ok(da_dtype) || !dt_ok(az_dtype)) return CPLXAMD_EINVAL;
   const bool cols_mode = (mode & CPLXAMD_L0_COLS) != 0, train = (mode & CPLXAMD_L0_TRAIN) != 0;
   const int64_t n = rows * (int64_t)cols;
-  if (n == 0) return 0;
+  if (n == 0) {
+    // no rows to sum: the per-column gradient is 0, not whatever the caller's buffer held (a memset node when captured)
+    if (cols_mode && cols > 0) return (int)hipMemsetAsync(d_log_alpha, 0, (size_t)cols * sizeof(float), (hipStream_t)stream);
+    return 0;
+  }
   if (!al16p(d) || !al16p(a) || !al16p(log_alpha) || !al16p(da) || !al16p(az) || !al16p(d_log_alpha) ||
       (train && !al16p(u)) || !al16p(ws))
     return CPLXAMD_EALIGN;

@@ -336,6 +336,7 @@ template <typename T, typename TS>
 static int launch_fwd(const void* mu_r, const void* mu_i, const void* s2, const void* eps_r,
                       const void* eps_i, uint64_t seed, uint64_t offset, const uint64_t* state,
                       void* y_r, void* y_i, int64_t n, hipStream_t st) {
+  if (n == 0) return 0;                      // an empty operand: nothing to launch
   const int grid = stream_grid(n >> 3, kRpThreads);
   const bool cplx = mu_i != nullptr, philox = eps_r == nullptr;
 #define RP_FWD(C, P)                                                                       \
@@ -355,6 +356,7 @@ template <typename T, typename TG, typename TS>
 static int launch_bwd(const void* g_r, const void* g_i, const void* s2, const void* eps_r,
                       const void* eps_i, uint64_t seed, uint64_t offset, const uint64_t* state,
                       void* g_s2, int64_t n, hipStream_t st) {
+  if (n == 0) return 0;
   const int grid = stream_grid(n >> 3, kRpThreads);
   const bool cplx = g_i != nullptr, philox = eps_r == nullptr;
 #define RP_BWD(C, P)                                                                      \
@@ -491,6 +493,7 @@ int cplxamd_philox_advance(uint64_t* state, uint64_t* used, void* stream) {
 int cplxamd_philox_normal(float* eps_r, float* eps_i, uint64_t seed, uint64_t offset,
                           int64_t n, void* stream) {
   if (!eps_r || n < 0) return CPLXAMD_EINVAL;
+  if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int grid = stream_grid(n, kRpThreads);
   if (eps_i)
