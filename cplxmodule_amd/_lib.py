@@ -247,6 +247,8 @@ class EinsumDesc(ctypes.Structure):
                 ("stride_b", (c_int64 * 8) * 4), ("stride_c", (c_int64 * 8) * 4)]
 
 
+# The descriptors of the signal kernels (Fft, FftConv, Upfirdn, Iir, FiltFilt) carry up to three batch runs: _runs.py fuses
+# the dims into runs and writes them here (`fill`), csrc/runs.h decodes them (`decode_runs`).
 class FftDesc(ctypes.Structure):
     """cplxamd_fft_desc: one transformed dim (n, n_in, element strides) and up to three batch runs, run 0 outermost."""
     _fields_ = [("n", c_int64), ("n_in", c_int64), ("x_es", c_int64), ("y_es", c_int64), ("runs", ctypes.c_int32),
@@ -324,18 +326,17 @@ FILTFILT_REVERSE, FILTFILT_SCALE = 1, 2
 
 # function codes of cplxamd_cplx_fn_fwd / _bwd (CPLXAMD_FN_*)
 CPLX_FN = {"exp": 0, "log": 1, "sin": 2, "cos": 3, "tan": 4, "sinh": 5, "cosh": 6, "tanh": 7}
-_RESTYPES = {"cplxamd_stft_src": c_int64, "cplxamd_absmax_ws_bytes": c_int64, "cplxamd_init_ws_bytes": c_int64, "cplxamd_conv2d_cl2_mom_chunks": c_int64, "cplxamd_conv2d_cl2_mom_chunks_fl": c_int64, "cplxamd_vd_kl_ws_bytes": c_int64, "cplxamd_lrt_reparam_bwd_cols_ws_bytes": c_int64, "cplxamd_l0_gate_bwd_ws_bytes": c_int64, "cplxamd_bn_ws_bytes": c_int64,
-             "cplxamd_conv2d_wgrad_ws_bytes": c_int64, "cplxamd_conv2d_bf16_wgrad_ws_bytes": c_int64, "cplxamd_colsum_ws_bytes": c_int64, "cplxamd_gemm_ws_bytes": c_int64,
-             "cplxamd_cgemm3m_ws_bytes": c_int64,
-             "cplxamd_live_index_ws_bytes": c_int64,
-             "cplxamd_conv3d_wgrad_ws_bytes": c_int64,
-             "cplxamd_conv2d_nhwc_wgrad_ws_bytes": c_int64,
-             "cplxamd_conv2d_nhwc_wgrad_f32_ws_bytes": c_int64,
-             "cplxamd_conv2d_cl_pack_bytes": c_int64, "cplxamd_conv2d_cl_ws_bytes": c_int64,
-             "cplxamd_conv2d_cl_wgrad_ws_bytes": c_int64, "cplxamd_conv2d_clh_wgrad_ws_bytes": c_int64,
-
-             "cplxamd_conv2d_clr_pack_bytes": c_int64,
-             "cplxamd_conv2d_clr_ws_bytes": c_int64, "cplxamd_conv2d_clr_wgrad_ws_bytes": c_int64}
+# entry points that return an int64 (a count or a size in bytes) instead of an error code
+_RESTYPES = dict.fromkeys((
+    "cplxamd_stft_src", "cplxamd_absmax_ws_bytes", "cplxamd_init_ws_bytes", "cplxamd_conv2d_cl2_mom_chunks",
+    "cplxamd_conv2d_cl2_mom_chunks_fl", "cplxamd_vd_kl_ws_bytes", "cplxamd_lrt_reparam_bwd_cols_ws_bytes",
+    "cplxamd_l0_gate_bwd_ws_bytes", "cplxamd_bn_ws_bytes", "cplxamd_conv2d_wgrad_ws_bytes",
+    "cplxamd_conv2d_bf16_wgrad_ws_bytes", "cplxamd_colsum_ws_bytes", "cplxamd_gemm_ws_bytes",
+    "cplxamd_cgemm3m_ws_bytes", "cplxamd_live_index_ws_bytes", "cplxamd_conv3d_wgrad_ws_bytes",
+    "cplxamd_conv2d_nhwc_wgrad_ws_bytes", "cplxamd_conv2d_nhwc_wgrad_f32_ws_bytes", "cplxamd_conv2d_cl_pack_bytes",
+    "cplxamd_conv2d_cl_ws_bytes", "cplxamd_conv2d_cl_wgrad_ws_bytes", "cplxamd_conv2d_clh_wgrad_ws_bytes",
+    "cplxamd_conv2d_clr_pack_bytes", "cplxamd_conv2d_clr_ws_bytes", "cplxamd_conv2d_clr_wgrad_ws_bytes",
+), c_int64)
 
 _lib = None
 

@@ -12,6 +12,7 @@
 #pragma once
 #include "common.h"
 #include "launch.h"
+#include "runs.h"
 
 #include <type_traits>
 
@@ -329,18 +330,13 @@ __device__ __forceinline__ void batch_offsets(const Batch& b, int64_t v, int64_t
   yo = i0 * b.ys[0] + i1 * b.ys[1] + i2 * b.ys[2];
 }
 
-// the batch of a descriptor: its runs right-aligned (the innermost run is run 2)
+// the batch of a descriptor: its runs right-aligned (the innermost run is run 2), strides of any sign, an empty inner
+// run as one of size 1 (total is 0: nothing is launched)
 inline int batch_of(const cplxamd_fft_desc& d, Batch& b) {
-  b = Batch{1, 1, 1, {0, 0, 0}, {0, 0, 0}};
-  int64_t size[3] = {1, 1, 1};
-  for (int r = 0; r < d.runs; ++r) {
-    const int s = 3 - d.runs + r;
-    if (d.size[r] < 0) return CPLXAMD_EINVAL;
-    size[s] = d.size[r];
-    b.xs[s] = d.x_stride[r];
-    b.ys[s] = d.y_stride[r];
-    if (__builtin_mul_overflow(b.total, d.size[r], &b.total)) return CPLXAMD_ESHAPE;
-  }
+  using D = cplxamd_fft_desc;
+  int64_t size[3];
+  const RunStride<D> f[] = {{&D::x_stride, b.xs}, {&D::y_stride, b.ys}};
+  if (const int e = decode_runs(d, f, size, b.total, true)) return e;
   b.s1 = size[1] > 0 ? size[1] : 1;
   b.s2 = size[2] > 0 ? size[2] : 1;
   return 0;

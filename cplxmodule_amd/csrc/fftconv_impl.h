@@ -1,7 +1,8 @@
-// Overlap-save convolution on the FFT engine: the plan, the batch runs, the kernels and the launch templates of
+// Overlap-save convolution on the FFT engine: the plan, the kernels and the launch templates of
 // fftconv.hip (which describes them) and fftconv_wgrad.hip, as a header so that the two build side by side.
 #pragma once
 #include "fft_impl.h"
+#include "runs.h"
 
 namespace cplxamd {
 namespace sp {
@@ -110,58 +111,6 @@ inline int conv_plan_for(int64_t A, int64_t K, int64_t start, int64_t C, int64_t
   p.woff_part = al256(p.Lw * cs);
   p.wbytes = p.woff_part + al256(one * p.chunks);
   return 0;
-}
-
-// ---- the batch: three runs, right-aligned (unused ones have size 1 and stride 0) -----------------------------------------
-struct ConvRuns {
-  int64_t rows, size[3], as[3], bs[3], ys[3];
-};
-inline int conv_runs(const cplxamd_fftconv_desc& d, ConvRuns& r) {
-  if (d.runs < 0 || d.runs > 3) return CPLXAMD_EINVAL;
-  r = ConvRuns{1, {1, 1, 1}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  for (int q = 0; q < d.runs; ++q) {
-    const int s = 3 - d.runs + q;
-    if (d.size[q] < 0 || d.a_stride[q] < 0 || d.b_stride[q] < 0 || d.y_stride[q] < 0) return CPLXAMD_EINVAL;
-    r.size[s] = d.size[q];
-    r.as[s] = d.a_stride[q];
-    r.bs[s] = d.b_stride[q];
-    r.ys[s] = d.y_stride[q];
-    if (__builtin_mul_overflow(r.rows, d.size[q], &r.rows)) return CPLXAMD_ESHAPE;
-  }
-  return 0;
-}
-// the runs (of more than one row) whose `key` stride is non-zero (`want`) or zero, right-aligned into sel (-1: none);
-// returns the product of their sizes
-inline int64_t select_runs(const ConvRuns& r, const int64_t* key, bool want, int (&sel)[3]) {
-  int n = 0, tmp[3];
-  int64_t count = 1;
-  for (int s = 0; s < 3; ++s)
-    if (r.size[s] != 1 && (key[s] != 0) == want) {
-      tmp[n++] = s;
-      count *= r.size[s];
-    }
-  for (int s = 0; s < 3; ++s) sel[s] = s >= 3 - n ? tmp[s - (3 - n)] : -1;
-  return count;
-}
-// three runs of a kernel argument: sizes of runs 1 and 2, two strides per run
-struct Sub {
-  int64_t s1, s2, p[3], q[3];
-};
-inline Sub sub_runs(const ConvRuns& r, const int (&sel)[3], const int64_t* p, const int64_t* q) {
-  Sub o{1, 1, {0, 0, 0}, {0, 0, 0}};
-  for (int s = 0; s < 3; ++s)
-    if (sel[s] >= 0) {
-      o.p[s] = p[sel[s]];
-      o.q[s] = q[sel[s]];
-      if (s == 1) o.s1 = r.size[sel[s]];
-      if (s == 2) o.s2 = r.size[sel[s]];
-    }
-  return o;
-}
-__device__ __forceinline__ void sub_offsets(const Sub& b, int64_t v, int64_t& po, int64_t& qo) {
-  const int64_t i2 = v % b.s2, w = v / b.s2, i1 = w % b.s1, i0 = w / b.s1;
-  po = i0 * b.p[0] + i1 * b.p[1] + i2 * b.p[2];
-  qo = i0 * b.q[0] + i1 * b.q[1] + i2 * b.q[2];
 }
 
 // a null imaginary plane is a plane of zeros that is never read
@@ -405,7 +354,9 @@ inline int conv_check(const void* a_r, const void* b_r, const void* y_r, const c
                       int dtype, bool wgrad, ConvRuns& r, int64_t& filters, int (&kept)[3], ConvPlan& p) {
   if (!a_r || !b_r || !y_r || !d || !ws) return CPLXAMD_EINVAL;
   if (d->a_es < 0 || d->b_es < 0 || d->reserved != 0 || (wgrad && d->conj != 0)) return CPLXAMD_EINVAL;
-  if (const int e = conv_runs(*d, r)) return e;
+  using D = cplxamd_fftconv_desc;
+  const RunStride<D> f[] = {{&D::a_stride, r.as}, {&D::b_stride, r.bs}, {&D::y_stride, r.ys}};
+  if (const int e = decode_runs(*d, f, r.size, r.rows)) return e;
   filters = select_runs(r, wgrad ? r.ys : r.bs, true, kept);
   if (const int e = conv_plan_for(d->a_len, d->k, d->start, d->c_len, r.rows, filters, dtype, d->conj, d->log_l, p)) return e;
   if (p.path != CPLXAMD_FFTCONV_FUSED) return CPLXAMD_EINVAL;

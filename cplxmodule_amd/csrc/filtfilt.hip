@@ -10,6 +10,7 @@
 // rounded in between), workspace reversed -> y (the interior only, the operands' dtype).  Every rule of iir.hip holds:
 // one wave per workgroup, no workgroup waits for another, no atomics, no library state, nothing read on the host.
 #include "iir_impl.h"
+#include "runs.h"
 
 using namespace cplxamd;
 using namespace cplxamd::sp;
@@ -108,17 +109,11 @@ int cplxamd_filtfilt_pass(const void* x_r, const void* x_i, const void* c_r, con
   if (d->segments < 1 || d->seg_len < 1 || d->segments > nlog) return CPLXAMD_EINVAL;
   if (y_r && (d->y_lo < 0 || d->y_n < 1 || d->y_lo > nlog || d->y_n > nlog - d->y_lo)) return CPLXAMD_EINVAL;
   if ((d->flags & CPLXAMD_FILTFILT_SCALE) && (!zi_r || d->segments != 1)) return CPLXAMD_EINVAL;
-  if (d->runs < 0 || d->runs > 3) return CPLXAMD_EINVAL;
-  cplxamd_iir_desc id{};
-  id.runs = d->runs;
-  int64_t zs[3] = {0, 0, 0};
-  for (int q = 0; q < d->runs; ++q) {
-    if (d->z_stride[q] < 0) return CPLXAMD_EINVAL;
-    id.size[q] = d->size[q], id.x_stride[q] = d->x_stride[q], id.c_stride[q] = d->c_stride[q], id.y_stride[q] = d->y_stride[q];
-    zs[3 - d->runs + q] = d->z_stride[q];
-  }
+  using D = cplxamd_filtfilt_desc;
   ConvRuns r;
-  if (const int e = iir_runs(id, r)) return e;
+  int64_t zs[3];
+  const RunStride<D> f[] = {{&D::x_stride, r.as}, {&D::c_stride, r.bs}, {&D::z_stride, zs}, {&D::y_stride, r.ys}};
+  if (const int e = decode_runs(*d, f, r.size, r.rows)) return e;
   IirPlan p;
   if (const int e = ext_plan_for(d->n, d->edge, d->order, d->sections, r.rows, 1, in_dtype, cplx, d->segments, p)) return e;
   // the descriptor's own cut of the extended row: every sample in exactly one non-empty segment

@@ -101,7 +101,9 @@ int cplxamd_iir(const void* x_r, const void* x_i, const void* c_r, const void* c
   if (d->x_es < 0 || (d->flags & ~(CPLXAMD_IIR_REVERSE | CPLXAMD_IIR_CONJ)) != 0) return CPLXAMD_EINVAL;
   if (d->segments < 1 || d->seg_len < 1 || d->n < 1 || d->segments > d->n) return CPLXAMD_EINVAL;
   ConvRuns r;
-  if (const int e = iir_runs(*d, r)) return e;
+  using D = cplxamd_iir_desc;
+  const RunStride<D> f[] = {{&D::x_stride, r.as}, {&D::c_stride, r.bs}, {&D::y_stride, r.ys}};
+  if (const int e = decode_runs(*d, f, r.size, r.rows)) return e;
   IirPlan p;
   if (const int e = iir_plan_for(d->n, d->order, d->sections, r.rows, 1, dtype, cplx, d->segments, p)) return e;
   // the descriptor's own cut of the row: every sample in exactly one non-empty segment

@@ -1,7 +1,8 @@
 // Recursive filtering on a chunk-parallel kernel: the plan, the kernels and the checks of iir.hip (which describes
-// them).  The batch runs are fftconv_impl.h's.
+// them).  The batch runs are runs.h's.
 #pragma once
-#include "fftconv_impl.h"
+#include "fft_engine.h"
+#include "runs.h"
 
 namespace cplxamd {
 namespace sp {
@@ -417,21 +418,6 @@ __global__ __launch_bounds__(kET) void iir_scan(const T* zr, const T* zi, const 
     }
     for (int i = 0; i < w; ++i) cr[i] = nr[i], ci[i] = ni[i];
   }
-}
-
-inline int iir_runs(const cplxamd_iir_desc& d, ConvRuns& r) {
-  if (d.runs < 0 || d.runs > 3) return CPLXAMD_EINVAL;
-  r = ConvRuns{1, {1, 1, 1}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  for (int q = 0; q < d.runs; ++q) {
-    const int s = 3 - d.runs + q;
-    if (d.size[q] < 0 || d.x_stride[q] < 0 || d.c_stride[q] < 0 || d.y_stride[q] < 0) return CPLXAMD_EINVAL;
-    r.size[s] = d.size[q];
-    r.as[s] = d.x_stride[q];
-    r.bs[s] = d.c_stride[q];
-    r.ys[s] = d.y_stride[q];
-    if (__builtin_mul_overflow(r.rows, d.size[q], &r.rows)) return CPLXAMD_ESHAPE;
-  }
-  return 0;
 }
 
 }  // namespace sp

@@ -1,8 +1,9 @@
 // Rational rate change on direct-form polyphase kernels: the plan, the kernels and the checks of upfirdn.hip (which
-// describes them) and upfirdn_wgrad.hip, as a header so that the two build side by side.  The batch runs are
-// fftconv_impl.h's.
+// describes them) and upfirdn_wgrad.hip, as a header so that the two build side by side.  The batch runs are runs.h's;
+// the weight gradient's chunking constants are fftconv_impl.h's.
 #pragma once
 #include "fftconv_impl.h"
+#include "runs.h"
 
 namespace cplxamd {
 namespace sp {
@@ -117,21 +118,6 @@ inline int up_plan_for(int64_t A, int64_t K, int64_t C, int64_t up, int64_t down
   p.wbytes = al256(one * p.chunks);
   int64_t wgs;
   if (__builtin_mul_overflow(nf * p.chunks, p.kblocks, &wgs) || wgs > 0x7fffffffll) return CPLXAMD_ESHAPE;
-  return 0;
-}
-
-inline int up_runs(const cplxamd_upfirdn_desc& d, ConvRuns& r) {
-  if (d.runs < 0 || d.runs > 3) return CPLXAMD_EINVAL;
-  r = ConvRuns{1, {1, 1, 1}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  for (int q = 0; q < d.runs; ++q) {
-    const int s = 3 - d.runs + q;
-    if (d.size[q] < 0 || d.a_stride[q] < 0 || d.b_stride[q] < 0 || d.y_stride[q] < 0) return CPLXAMD_EINVAL;
-    r.size[s] = d.size[q];
-    r.as[s] = d.a_stride[q];
-    r.bs[s] = d.b_stride[q];
-    r.ys[s] = d.y_stride[q];
-    if (__builtin_mul_overflow(r.rows, d.size[q], &r.rows)) return CPLXAMD_ESHAPE;
-  }
   return 0;
 }
 
@@ -407,7 +393,9 @@ inline int up_check(const void* a_r, const void* a_i, const void* b_r, const voi
                     UpPlan& p) {
   if (!a_r || !b_r || !y_r || !d) return CPLXAMD_EINVAL;
   if (d->a_es < 0 || d->b_es < 0 || (wgrad && d->conj != 0)) return CPLXAMD_EINVAL;
-  if (const int e = up_runs(*d, r)) return e;
+  using D = cplxamd_upfirdn_desc;
+  const RunStride<D> f[] = {{&D::a_stride, r.as}, {&D::b_stride, r.bs}, {&D::y_stride, r.ys}};
+  if (const int e = decode_runs(*d, f, r.size, r.rows)) return e;
   filters = select_runs(r, wgrad ? r.ys : r.bs, true, kept);
   if (const int e = up_plan_for(d->a_len, d->k, d->c_len, d->up, d->down, d->off, r.rows, filters, dtype, d->conj,
                                 a_i != nullptr, b_i != nullptr, p))

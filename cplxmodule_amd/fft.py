@@ -3,8 +3,8 @@ handling, the launch glue and the autograd Function behind cplx.fft / ifft / fft
 
 One launch of `cplxamd_fft` transforms every vector of a tensor along ONE dim, reading both planes where they lie:
 the dims other than the transformed one are sorted by stride and fused into at most three batch runs, jointly for the
-input and the output (a contiguous, channels-last, transposed, sliced or `expand`ed input needs no copy); planes that
-share no layout, or that need more than three runs, are copied once, differentiably.  The output has the input's memory
+input and the output (_runs.py; a contiguous, channels-last, transposed, sliced or `expand`ed input needs no copy); planes
+that share no layout, or that need more than three runs, are copied once, differentiably.  The output has the input's memory
 order.  `n` larger than the extent is zero padding inside the kernel's loader, `n` smaller a `narrow` view.  A transform
 over several dims is one launch per dim, the last listed dim first; for bf16 planes every intermediate is float32, so
 the result is rounded once.
@@ -22,6 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import CplxAmdError, call, ptr, require_device, stream_ptr
+from ._runs import code, dense_like, fill, fit_like, runs
 
 MAX_N = 1 << 22                       # CPLXAMD_WELCH_MAX_N
 PATHS = ("direct", "four-step", "bluestein", "bluestein+four-step")   # cplxamd_fft_plan's return codes
@@ -29,50 +30,18 @@ NORMS = (None, "backward", "ortho", "forward")
 _ONE_PER_WORKGROUP = False            # private: True runs packed lengths with one vector per workgroup (scripts/bench_fft.py only)
 
 
-def _code(dtype):
-    if dtype == torch.float32:
-        return _lib.F32
-    if dtype == torch.bfloat16:
-        return _lib.BF16
-    if dtype == torch.float64:
-        return _lib.F64
-    raise CplxAmdError(f"fft: planes must be float32, bfloat16 or float64, got {dtype}")
-
-
 def plan(n, vectors, dtype=torch.float32):
     """(path, vectors per workgroup, workspace bytes) of a length-n transform of `vectors` vectors whose input planes
     have `dtype` -- a pure host call, no GPU needed.  Raises CplxAmdError when n is outside [1, 2^22]."""
     vpw, ws = ctypes.c_int(0), ctypes.c_int64(0)
-    rc = _lib.load().cplxamd_fft_plan(int(n), int(vectors), _code(dtype), ctypes.byref(vpw), ctypes.byref(ws))
+    rc = _lib.load().cplxamd_fft_plan(int(n), int(vectors), code(dtype), ctypes.byref(vpw), ctypes.byref(ws))
     if rc < 0:
         raise CplxAmdError(f"fft: transform length {n} is outside [1, 2^22 = {MAX_N}], the lengths the kernels support")
     return PATHS[rc], vpw.value, ws.value
 
 
-def _dense_like(t, dim, n):
-    """(shape, strides) of the output for input plane t: t's shape with `n` along `dim`, dense, in t's memory order
-    (what empty_like gives a dense t)"""
-    shape = list(t.shape)
-    shape[dim] = n
-    order = sorted(range(t.dim()), key=lambda d: (-t.stride(d), d))
-    strides, acc = [0] * t.dim(), 1
-    for d in reversed(order):
-        strides[d] = acc
-        acc *= max(shape[d], 1)
-    return shape, strides
-
-
-def _runs(shape, xs, ys, dim):
-    """the dims other than `dim` as batch runs [size, x stride, y stride], outermost first: sorted by the output's
-    stride and fused where both tensors allow it"""
-    dims = sorted((d for d in range(len(shape)) if d != dim and shape[d] != 1), key=lambda d: -ys[d])
-    runs = []
-    for d in dims:
-        if runs and runs[-1][1] == xs[d] * shape[d] and runs[-1][2] == ys[d] * shape[d]:
-            runs[-1] = [runs[-1][0] * shape[d], xs[d], ys[d]]
-        else:
-            runs.append([shape[d], xs[d], ys[d]])
-    return runs
+_dense_like = dense_like                              # the names the tests know the run rule of one skipped dim by
+_runs = lambda shape, xs, ys, dim: runs(shape, (xs, ys), dim)        # noqa: E731
 
 
 class _Transform(torch.autograd.Function):
@@ -81,27 +50,25 @@ class _Transform(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pr, pi, meta):
-        n, dim, inverse, scale, out_dtype = meta
-        ctx.meta = meta
+        n, dim, inverse, scale, out_dtype, batch, ys = meta
+        ctx.meta = meta[:4]
         ctx.src = (pr.shape[dim], pr.dtype)
-        yr = torch.empty_strided(*_dense_like(pr, dim, n), dtype=out_dtype, device=pr.device)
+        yr = torch.empty_strided(pr.shape[:dim] + (n,) + pr.shape[dim + 1:], ys, dtype=out_dtype, device=pr.device)
         yi = torch.empty_like(yr)
         if yr.numel() == 0:
             return yr, yi
-        runs = _runs(yr.shape, pr.stride(), yr.stride(), dim)
-        d = _lib.FftDesc(n=n, n_in=min(n, pr.shape[dim]), x_es=pr.stride(dim), y_es=yr.stride(dim), runs=len(runs),
+        d = _lib.FftDesc(n=n, n_in=min(n, pr.shape[dim]), x_es=pr.stride(dim), y_es=yr.stride(dim),
                          inverse=(1 if inverse else 0) | (2 if _ONE_PER_WORKGROUP else 0), scale=scale)
-        for r, (size, xs, ys) in enumerate(runs):
-            d.size[r], d.x_stride[r], d.y_stride[r] = size, xs, ys
-        _, _, ws_bytes = plan(n, yr.numel() // n, pr.dtype)
+        vectors, _ = fill(d, batch, ("x_stride", "y_stride"))
+        _, _, ws_bytes = plan(n, vectors, pr.dtype)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pr.device)
-        call("cplxamd_fft", ptr(pr), ptr(pi), ptr(yr), ptr(yi), ctypes.byref(d), _code(pr.dtype), _code(out_dtype),
+        call("cplxamd_fft", ptr(pr), ptr(pi), ptr(yr), ptr(yi), ctypes.byref(d), code(pr.dtype), code(out_dtype),
              ptr(ws), ws_bytes, stream_ptr())
         return yr, yi
 
     @staticmethod
     def backward(ctx, gr, gi):
-        n, dim, inverse, scale, _ = ctx.meta
+        n, dim, inverse, scale = ctx.meta
         extent, dtype = ctx.src
         dr, di = transform(gr, gi, n, dim, not inverse, scale, dtype)
         if extent < n:                                    # the adjoint of zero padding
@@ -115,9 +82,8 @@ def transform(pr, pi, n, dim, inverse, scale, out_dtype):
     extent = pr.shape[dim]
     if extent > n:                                        # truncation: a view (autograd pads its gradient)
         pr, pi = pr.narrow(dim, 0, n), pi.narrow(dim, 0, n)
-    if pr.stride() != pi.stride() or len(_runs(pr.shape, pr.stride(), _dense_like(pr, dim, n)[1], dim)) > 3:
-        pr, pi = pr.contiguous(), pi.contiguous()         # one differentiable copy
-    return _Transform.apply(pr, pi, (n, dim, bool(inverse), float(scale), out_dtype))
+    pr, pi, batch, ys = fit_like(pr, pi, dim, n)          # at most one differentiable copy
+    return _Transform.apply(pr, pi, (n, dim, bool(inverse), float(scale), out_dtype, batch, ys))
 
 
 def _scale(n, norm, inverse):
@@ -170,7 +136,7 @@ def fftn(input, s, dim, norm, inverse, name):
     pr, pi = input.real, input.imag
     if pr.dtype != pi.dtype:
         raise CplxAmdError(f"{name}: the planes have different dtypes: {pr.dtype} and {pi.dtype}")
-    _code(pr.dtype)
+    code(pr.dtype)
     for _, n in todo:
         if n > MAX_N:
             raise CplxAmdError(f"{name}: length {n} exceeds 2^22 = {MAX_N}, the longest transform supported")

@@ -15,7 +15,7 @@ operand is a null imaginary plane (never read, no zero plane allocated); the gra
 (the null output plane is not stored).
 
 Leading dims broadcast by torch's rules and are read where they lie: they are sorted by stride and fused into at most
-three batch runs jointly for both operands and the result (as fft.py's `_runs`), so contiguous, step-sliced, `expand`ed
+three batch runs jointly for both operands and the result (_runs.py: `runs`, `fit`), so contiguous, step-sliced, `expand`ed
 and transposed operands need no copy; an operand whose planes share no layout, or that needs more than three runs, is
 copied once, differentiably.  The workspace (twiddles, filter spectra, partial spectra) comes from torch's allocator and
 nothing reads a device value on the host: calls can be captured in a hipGraph.
@@ -30,7 +30,8 @@ import torch
 
 from . import _lib
 from ._lib import CplxAmdError, call, ptr, require_device, stream_ptr
-from .fft import MAX_N, _code
+from ._runs import code, dense, fill, fit, fit_wgrad, planes
+from .fft import MAX_N
 
 MODES = ("full", "same", "valid")
 PATHS = ("fused", "composed")                              # cplxamd_fftconv_plan's return codes
@@ -43,7 +44,7 @@ def plan(a_len, k, start, length, rows=1, filters=1, dtype=torch.float32, conj=F
     stride S, blocks per row, blocks per workgroup, the block's offsets, workspace bytes; the same for the weight
     gradient with its chunks).  `log_l` forces L = 2^log_l >= k (measurements and exact tests)."""
     out = (ctypes.c_int64 * len(_lib.FFTCONV_PLAN_FIELDS))()
-    rc = _lib.load().cplxamd_fftconv_plan(int(a_len), int(k), int(start), int(length), int(rows), int(filters), _code(dtype),
+    rc = _lib.load().cplxamd_fftconv_plan(int(a_len), int(k), int(start), int(length), int(rows), int(filters), code(dtype),
                                           int(bool(conj)), int(log_l or 0), out)
     if rc == -3 and k <= FUSED_MAX_K:
         raise CplxAmdError(f"fftconvolve: {rows} rows and {filters} filters of lengths {a_len} and {k} need more blocks or "
@@ -68,54 +69,14 @@ def window(n, m, mode):
     return min(n, m) - 1, max(n, m) - min(n, m) + 1
 
 
-def _runs(shape, strides):
-    """the batch dims (all but the last) as runs [size, stride per tensor ...], outermost first: sorted by the LAST
-    tensor's strides (the result's) and fused where every tensor allows it"""
-    nd = len(shape) - 1
-    dims = sorted((d for d in range(nd) if shape[d] != 1), key=lambda d: tuple(-s[d] for s in reversed(strides)))
-    runs = []
-    for d in dims:
-        if runs and all(r == s[d] * shape[d] for r, s in zip(runs[-1][1:], strides)):
-            runs[-1] = [runs[-1][0] * shape[d]] + [s[d] for s in strides]
-        else:
-            runs.append([shape[d]] + [s[d] for s in strides])
-    return runs
-
-
-def _dense(shape):
-    strides, acc = [0] * len(shape), 1
-    for d in reversed(range(len(shape))):
-        strides[d] = acc
-        acc *= max(shape[d], 1)
-    return strides
-
-
-def _expanded_strides(t, shape):
-    return t.expand(shape).stride()
-
-
-def _share(pr, pi):
-    """planes of one operand must share a layout"""
-    if pi is not None and pr.stride() != pi.stride():
-        return pr.contiguous(), pi.contiguous()
-    return pr, pi
-
-
-def _launch(name, ar, ai, br, bi, yr, yi, shape, y_strides, a_len, k, c_len, start, conj, log_l, ws_key):
-    """one call of cplxamd_fftconv / _wgrad over the batch `shape[:-1]`; b is read with its broadcast strides"""
-    sa, sb = ar.stride(), _expanded_strides(br, shape[:-1] + (br.shape[-1],))
-    runs = _runs(shape, (sa, sb, y_strides))
-    d = _lib.FftConvDesc(a_len=a_len, k=k, c_len=c_len, start=start, a_es=sa[-1], b_es=sb[-1], runs=len(runs),
-                         conj=int(conj), log_l=int(log_l or 0), reserved=0)
-    rows, filters = 1, 1
-    for r, (size, xa, xb, xy) in enumerate(runs):
-        d.size[r], d.a_stride[r], d.b_stride[r], d.y_stride[r] = size, xa, xb, xy
-        rows *= size
-        if (xy if ws_key == "wgrad_ws_bytes" else xb) != 0:
-            filters *= size
+def _launch(name, ar, ai, br, bi, yr, yi, runs, a_len, k, c_len, start, conj, log_l, ws_key):
+    """one call of cplxamd_fftconv / _wgrad over the batch runs of (a, b, y); b is read with its broadcast strides"""
+    d = _lib.FftConvDesc(a_len=a_len, k=k, c_len=c_len, start=start, a_es=ar.stride(-1), b_es=br.stride(-1), conj=int(conj),
+                         log_l=int(log_l or 0), reserved=0)
+    rows, filters = fill(d, runs, ("a_stride", "b_stride", "y_stride"), "y_stride" if ws_key == "wgrad_ws_bytes" else "b_stride")
     ws_bytes = plan(a_len, k, start, c_len, rows, filters, ar.dtype, conj, log_l)[ws_key]
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=ar.device)
-    call(name, ptr(ar), ptr(ai), ptr(br), ptr(bi), ptr(yr), ptr(yi), ctypes.byref(d), _code(ar.dtype), ptr(ws), ws_bytes,
+    call(name, ptr(ar), ptr(ai), ptr(br), ptr(bi), ptr(yr), ptr(yi), ctypes.byref(d), code(ar.dtype), ptr(ws), ws_bytes,
          stream_ptr())
 
 
@@ -125,15 +86,14 @@ class _P1(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ar, ai, br, bi, meta):
-        start, length, conj, out_imag, log_l = meta
-        ctx.meta = meta
+        start, length, conj, out_imag, log_l, runs = meta
+        ctx.meta = meta[:5]
         ctx.save_for_backward(ar, ai, br, bi)
-        shape = tuple(ar.shape[:-1]) + (length,)
-        yr = torch.empty(shape, dtype=ar.dtype, device=ar.device)
+        yr = torch.empty(tuple(ar.shape[:-1]) + (length,), dtype=ar.dtype, device=ar.device)
         yi = torch.empty_like(yr) if out_imag else None
         if yr.numel():
-            _launch("cplxamd_fftconv", ar, ai, br, bi, yr, yi, shape, yr.stride(), ar.shape[-1], br.shape[-1], length, start,
-                    conj, log_l, "ws_bytes")
+            _launch("cplxamd_fftconv", ar, ai, br, bi, yr, yi, runs, ar.shape[-1], br.shape[-1], length, start, conj, log_l,
+                    "ws_bytes")
         return yr, yi
 
     @staticmethod
@@ -156,15 +116,14 @@ class _P2(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ar, ai, cr, ci, meta):
-        start, k, fshape, out_imag, log_l = meta
-        ctx.meta = meta
+        start, k, fshape, out_imag, log_l, runs = meta
+        ctx.meta = meta[:5]
         ctx.save_for_backward(ar, ai, cr, ci)
         yr = torch.empty(fshape + (k,), dtype=ar.dtype, device=ar.device)
         yi = torch.empty_like(yr) if out_imag else None
-        shape = tuple(ar.shape[:-1]) + (k,)
         if yr.numel() and ar.numel():
-            _launch("cplxamd_fftconv_wgrad", ar, ai, cr, ci, yr, yi, shape, _expanded_strides(yr, shape), ar.shape[-1], k,
-                    cr.shape[-1], start, False, log_l, "wgrad_ws_bytes")
+            _launch("cplxamd_fftconv_wgrad", ar, ai, cr, ci, yr, yi, runs, ar.shape[-1], k, cr.shape[-1], start, False, log_l,
+                    "wgrad_ws_bytes")
         elif yr.numel():                                  # no rows to sum
             yr.zero_()
             if yi is not None:
@@ -187,50 +146,20 @@ class _P2(torch.autograd.Function):
 def conv(ar, ai, br, bi, start, length, conj=False, out_imag=True, log_l=None):
     """P1 on planes: a [*B, A] (views welcome), filter b [*Bb, K] with Bb broadcastable to B and as many dims -> (yr, yi)
     of [*B, length], yi None unless `out_imag`.  Differentiable to any order."""
-    ar, ai = _share(ar, ai)
-    br, bi = _share(br, bi)
     shape = tuple(ar.shape[:-1]) + (length,)
-    fshape = shape[:-1] + (br.shape[-1],)
-    if len(_runs(shape, (ar.stride(), _expanded_strides(br, fshape), _dense(shape)))) > 3:
-        ar, ai = ar.contiguous(), None if ai is None else ai.contiguous()     # one differentiable copy
-    if len(_runs(shape, (ar.stride(), _expanded_strides(br, fshape), _dense(shape)))) > 3:
-        br, bi = br.expand(fshape).contiguous(), None if bi is None else bi.expand(fshape).contiguous()
-    return _P1.apply(ar, ai, br, bi, (int(start), int(length), bool(conj), bool(out_imag), log_l))
+    ((ar, ai), (br, bi)), runs = fit(shape, [(ar, ai), (br, bi)], dense(shape), [(0,), (1,)])     # copies: a, then b expanded
+    return _P1.apply(ar, ai, br, bi, (int(start), int(length), bool(conj), bool(out_imag), log_l, runs))
 
 
 def wgrad(ar, ai, cr, ci, start, k, fshape, out_imag=True, log_l=None):
     """P2 on planes: a [*B, A], c [*B, C] -> (yr, yi) of [*fshape, k] (fshape broadcastable to B, as many dims): the
     rows that fshape broadcasts over are summed inside the kernel.  Differentiable to any order."""
-    ar, ai = _share(ar, ai)
-    cr, ci = _share(cr, ci)
-    batch = tuple(ar.shape[:-1])
-    shape = batch + (k,)
-
-    def too_many(f):
-        ys = torch.empty(tuple(f) + (k,), device="meta").expand(shape).stride()
-        return len(_runs(shape, (ar.stride(), cr.stride(), ys))) > 3
-
-    if too_many(fshape):
-        ar, ai = ar.contiguous(), None if ai is None else ai.contiguous()     # one differentiable copy each
-        cr, ci = cr.contiguous(), None if ci is None else ci.contiguous()
-    if too_many(fshape):                                  # the broadcast pattern itself: per-row results, summed by torch
-        yr, yi = _P2.apply(ar, ai, cr, ci, (int(start), int(k), batch, bool(out_imag), log_l))
-        to = tuple(fshape) + (k,)
-        return yr.sum_to_size(to), None if yi is None else yi.sum_to_size(to)
-    return _P2.apply(ar, ai, cr, ci, (int(start), int(k), tuple(fshape), bool(out_imag), log_l))
-
-
-def _planes(x, name):
-    from .cplx import Cplx
-    if isinstance(x, Cplx):
-        pr, pi = x.real, x.imag
-        if pr.dtype != pi.dtype:
-            raise CplxAmdError(f"fftconvolve: the planes of `{name}` have different dtypes: {pr.dtype} and {pi.dtype}")
-        return pr, pi
-    if torch.is_tensor(x) and not x.is_complex():
-        return x, None
-    raise CplxAmdError(f"fftconvolve: `{name}` is a {type(x).__name__}{' of complex dtype' if torch.is_tensor(x) else ''}, "
-                       "not a Cplx or a real torch.Tensor (wrap planes with Cplx(re, im); torch complex tensors are not taken)")
+    (ar, ai), (cr, ci), runs, f = fit_wgrad((ar, ai), (cr, ci), k, fshape)
+    yr, yi = _P2.apply(ar, ai, cr, ci, (int(start), int(k), f, bool(out_imag), log_l, runs))
+    if f == tuple(fshape):
+        return yr, yi
+    to = tuple(fshape) + (k,)                             # the broadcast pattern itself: per-row results, summed by torch
+    return yr.sum_to_size(to), None if yi is None else yi.sum_to_size(to)
 
 
 def _composed(ar, ai, br, bi, start, length, dtype):
@@ -256,7 +185,7 @@ def fftconvolve(input, other, mode="full", log_l=None):
     from .cplx import Cplx
     if mode not in MODES:
         raise ValueError(f"fftconvolve: mode must be one of {MODES}, got {mode!r}")
-    (xr, xi), (hr, hi) = _planes(input, "input"), _planes(other, "other")
+    (xr, xi), (hr, hi) = planes(input, "input", "fftconvolve"), planes(other, "other", "fftconvolve")
     for t, name in ((xr, "input"), (hr, "other")):
         if t.dim() == 0:
             raise ValueError(f"fftconvolve: `{name}` is 0-d: there is no dim to convolve along")
@@ -265,7 +194,7 @@ def fftconvolve(input, other, mode="full", log_l=None):
     batch = tuple(torch.broadcast_shapes(xr.shape[:-1], hr.shape[:-1]))       # RuntimeError, as torch raises it
     if xr.dtype != hr.dtype:
         raise CplxAmdError(f"fftconvolve: the operands have different dtypes: {xr.dtype} and {hr.dtype}")
-    _code(xr.dtype)
+    code(xr.dtype)
     n, m = xr.shape[-1], hr.shape[-1]
     start, length = window(n, m, mode)
     (ar, ai), (br, bi) = ((xr, xi), (hr, hi)) if n >= m else ((hr, hi), (xr, xi))

@@ -19,15 +19,13 @@ result is COMPOSED from the differentiable pieces: a torch extension, cplx.lfilt
 is not the hot path.
 """
 import ctypes
-import math
 
 import torch
 
 from . import _lib
 from . import iir as _iir
 from ._lib import CplxAmdError, call, ptr, require_device, stream_ptr
-from .fft import _code
-from .fftconv import _dense, _expanded_strides, _runs, _share
+from ._runs import code, dense, fill, fit
 from .iir import MAX_ORDER, MAX_SECTIONS, PATHS, _cdiv, _cmul, _ct, _lead, _needs_grad, _operands, _wrap
 
 PADTYPES = ("odd", "even", "constant", None)
@@ -51,7 +49,7 @@ def plan(n, edge, order, sections=1, rows=1, filters=1, dtype=torch.float32, cpl
     out = (ctypes.c_int64 * len(_lib.FILTFILT_PLAN_FIELDS))()
     force = _iir._FORCE_SEGMENTS if force_segments is None else force_segments
     rc = _lib.load().cplxamd_filtfilt_plan(int(n), int(edge), int(order), int(sections), int(rows), int(filters),
-                                           _code(dtype), int(bool(cplx)), int(force), out)
+                                           code(dtype), int(bool(cplx)), int(force), out)
     if rc == -3:
         raise CplxAmdError(f"filtfilt: rows of {n} + 2 * {edge} samples in {rows} rows exceed what the kernel indexes (2^40 "
                            "samples, 2^31 - 1 workgroups)")
@@ -152,11 +150,10 @@ def sosfilt_zi(sos):
 def _call(xr, xi, cr, ci, zr, zi, yr, yi, fr, fi, runs, n, edge, mode, y_lo, y_n, x_es, order, sections, segs, seg_len, flags,
           cx, in_dtype, out_dtype):
     d = _lib.FiltFiltDesc(n=n, edge=edge, y_lo=y_lo, y_n=y_n, order=order, sections=sections, segments=segs, seg_len=seg_len,
-                          x_es=x_es, runs=len(runs), flags=flags, mode=mode, reserved=0)
-    for r, (size, sx, sc, sz, sy) in enumerate(runs):
-        d.size[r], d.x_stride[r], d.c_stride[r], d.z_stride[r], d.y_stride[r] = size, sx, sc, sz, sy
+                          x_es=x_es, flags=flags, mode=mode, reserved=0)
+    fill(d, runs, ("x_stride", "c_stride", "z_stride", "y_stride"))
     call("cplxamd_filtfilt_pass", ptr(xr), ptr(xi), ptr(cr), ptr(ci), ptr(zr), ptr(zi), ptr(yr), ptr(yi), ptr(fr), ptr(fi),
-         ctypes.byref(d), int(cx), _code(in_dtype), _code(out_dtype), stream_ptr())
+         ctypes.byref(d), int(cx), code(in_dtype), code(out_dtype), stream_ptr())
 
 
 def _first(xr, xi, n, edge, mode, reverse, ct):
@@ -180,59 +177,33 @@ def run_pass(xr, xi, cr, ci, ur, ui, edge, mode, y_lo, y_n, reverse, cx, out_dty
     S, W = cr.shape[-2], cr.shape[-1]
     D = W // 2 - 1
     ct, dev, in_dtype = cr.dtype, xr.device, xr.dtype
-    rows, w = math.prod(batch), S * D
     yr = torch.empty(batch + (y_n,), dtype=out_dtype, device=dev)
     yi = torch.empty_like(yr) if cx else None
-    xr, xi = _share(xr, xi)
-    shape = batch + (n,)
-    flat = lambda t, k: None if t is None else t.reshape(tuple(t.shape[:-2]) + (S * k,))   # noqa: E731
-    joint = lambda: _runs(shape, (xr.stride(), _expanded_strides(flat(cr, W), batch + (S * W,)),   # noqa: E731
-                                  _expanded_strides(flat(ur, D), batch + (S * D,)), _dense(batch + (y_n,))))
-    if len(joint()) > 3:
-        xr, xi = xr.contiguous(), None if xi is None else xi.contiguous()
-    if len(joint()) > 3:
-        dense = lambda t, k: None if t is None else t.expand(batch + (S, k)).contiguous()  # noqa: E731
-        cr, ci, ur, ui = dense(cr, W), dense(ci, W), dense(ur, D), dense(ui, D)
-    c2r, c2i, u2r, u2i = flat(cr, W), flat(ci, W), flat(ur, D), flat(ui, D)
-    runs = joint()
-    kept = [r for r in runs if r[2] != 0]
-    filters = math.prod(r[0] for r in kept)
-    p = plan(n, edge, D, S, rows, filters, in_dtype, cx, force_segments)
-    segs, seg_len = p["segments"], p["seg_len"]
-    # the split path wants the rows that share a filter to be consecutive, and the filters to fit two batch runs
-    shared_inner = all(r[2] == 0 for r in runs[len(kept):]) and all(r[2] != 0 for r in runs[:len(kept)])
-    if segs == 1 or not (shared_inner and len(kept) <= 2):
-        segs, seg_len = 1, n + 2 * edge
+    # copies: x, then c and u expanded
+    ((xr, xi), (cr, ci), (ur, ui)), runs = fit(batch + (n,), [(xr, xi), (cr, ci), (ur, ui)], dense(batch + (y_n,)),
+                                               [(0,), (1, 2)])
     rev = _lib.FILTFILT_REVERSE if reverse else 0
     es = xr.stride(-1)
-    if segs == 1:
-        _call(xr, xi, c2r, c2i, u2r, u2i, yr, yi, None, None, runs, n, edge, mode, y_lo, y_n, es, D, S, 1, seg_len,
+
+    def launch(x, z, y, f, runs, n, segs, seg_len):
+        # the transition (null input) runs on the bare segment in the compute type; without y the window is a placeholder
+        bare = x[0] is None
+        lo, cnt = (0, 1) if y[0] is None else (y_lo, y_n)
+        _call(*x, cr, ci, *z, *y, *f, runs, n, 0 if bare else edge, mode, lo, cnt, 0 if bare else es, D, S, segs, seg_len, rev,
+              cx, ct if bare else in_dtype, ct if bare else out_dtype)
+
+    def enter():                                          # the scaled state enters the scan as the row's initial state
+        fr, fi = _first(xr, xi, n, edge, mode, reverse, ct)
+        full = lambda t: None if t is None else t.expand(batch + (S, D))          # noqa: E731
+        grow = lambda t: None if t is None else t[..., None, None]                # noqa: E731
+        s_r, s_i = _cmul(full(ur), full(ui), grow(fr), grow(fi))
+        flat = lambda t: None if t is None else t.expand(batch + (S, D)).reshape(-1, S * D).contiguous()   # noqa: E731
+        return flat(s_r), flat(s_i) if cx else None
+
+    if _iir.split(launch, call, lambda r, k: plan(n, edge, D, S, r, k, in_dtype, cx, force_segments), enter, (xr, xi), (yr, yi),
+                  runs, n, S, D, cx, ct, False) is None:
+        _call(xr, xi, cr, ci, ur, ui, yr, yi, None, None, runs, n, edge, mode, y_lo, y_n, es, D, S, 1, n + 2 * edge,
               rev | _lib.FILTFILT_SCALE, cx, in_dtype, out_dtype)
-        return yr, yi
-    new = lambda *s: torch.empty(s, dtype=ct, device=dev)  # noqa: E731
-    # 1. segment-final states from zero entering state (with `reverse`, segment 0 is the END of the extended row)
-    z_r, z_i = new(rows, segs, S, D), new(rows, segs, S, D) if cx else None
-    _call(xr, xi, c2r, c2i, None, None, None, None, z_r, z_i, runs, n, edge, mode, 0, 1, es, D, S, segs, seg_len, rev, cx,
-          in_dtype, out_dtype)
-    # 2. the transition of a full segment: unit entering states on null input, one row per (filter, unit state)
-    eye = torch.eye(w, dtype=ct, device=dev).reshape(1, w, 1, S, D).expand(filters, w, 1, S, D).contiguous()
-    m_r, m_i = new(filters * w, 1, S, D), new(filters * w, 1, S, D) if cx else None
-    mruns = [[r[0], 0, r[2], 0, 0] for r in kept] + [[w, 0, 0, 0, 0]]
-    _call(None, None, c2r, c2i, eye, None, None, None, m_r, m_i, mruns, seg_len, 0, mode, 0, 1, 0, D, S, 1, seg_len, rev, cx,
-          ct, ct)
-    # 3. the entering state of every segment: the scaled state enters the scan as the row's initial state
-    fr, fi = _first(xr, xi, n, edge, mode, reverse, ct)
-    full = lambda t: None if t is None else t.expand(batch + (S, D))          # noqa: E731
-    grow = lambda t: None if t is None else t[..., None, None]                # noqa: E731
-    s_r, s_i = _cmul(full(ur), full(ui), grow(fr), grow(fi))
-    dense = lambda t: None if t is None else t.expand(batch + (S, D)).reshape(rows, w).contiguous()   # noqa: E731
-    s_r, s_i = dense(s_r), dense(s_i) if cx else None
-    e_r, e_i = new(rows, segs, S, D), new(rows, segs, S, D) if cx else None
-    call("cplxamd_iir_scan", ptr(z_r), ptr(z_i), ptr(m_r), ptr(m_i), ptr(s_r), ptr(s_i), ptr(e_r), ptr(e_i), rows,
-         rows // max(filters, 1), segs, w, int(cx), _code(ct), stream_ptr())
-    # 4. every segment from its true entering state
-    _call(xr, xi, c2r, c2i, e_r, e_i, yr, yi, None, None, runs, n, edge, mode, y_lo, y_n, es, D, S, segs, seg_len, rev, cx,
-          in_dtype, out_dtype)
     return yr, yi
 
 

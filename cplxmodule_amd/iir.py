@@ -17,7 +17,7 @@ gradient.  The final state zf is returned by the kernel; where a gradient may fl
 samples:  zf[i] = sum_{k > i} b_k x[N + i - k] - a_k y[N + i - k]  (+ zi[i + N] when N < D), with torch on D-sized slices.
 
 A real operand is a null imaginary plane (never read, no zero plane allocated); all-real operands run the real kernels.
-Leading dims broadcast by torch's rules and are read where they lie, under fftconv.py's rule of three batch runs,
+Leading dims broadcast by torch's rules and are read where they lie, under _runs.py's rule of three batch runs,
 otherwise one differentiable copy.  State planes are kept in the compute type (float32 for bfloat16 operands) and rounded
 once.  Workspaces come from torch's allocator and nothing reads a device value on the host: calls can be captured in a
 hipGraph.
@@ -25,7 +25,8 @@ hipGraph.
 Long rows with few rows take the SPLIT path (the plan decides; `_FORCE_SEGMENTS` forces it): each row is cut into
 segments, and four launches of the primitive and of a tiny scan kernel replace the one launch -- segment-final states
 from zero entering state; the segment transition matrix from unit entering states on null input; a sequential scan of
-the segments of each row; the run from the true entering states.  No workgroup waits for another inside a launch.
+the segments of each row; the run from the true entering states (`split`, which filtfilt.py runs with its own launcher).
+No workgroup waits for another inside a launch.
 """
 import ctypes
 import math
@@ -34,8 +35,7 @@ import torch
 
 from . import _lib
 from ._lib import CplxAmdError, call, ptr, require_device, stream_ptr
-from .fft import _code
-from .fftconv import _dense, _expanded_strides, _runs, _share
+from ._runs import code, dense, fill, fit, planes, share
 
 PATHS = ("row", "split")                                   # cplxamd_iir_plan's return codes
 MAX_ORDER = 8                                              # states of one direct-form section
@@ -49,7 +49,7 @@ def plan(n, order, sections=1, rows=1, filters=1, dtype=torch.float32, cplx=True
     segments, seg_len, compiled states, LDS bytes, threads, grid, workspace bytes of the split path)."""
     out = (ctypes.c_int64 * len(_lib.IIR_PLAN_FIELDS))()
     force = _FORCE_SEGMENTS if force_segments is None else force_segments
-    rc = _lib.load().cplxamd_iir_plan(int(n), int(order), int(sections), int(rows), int(filters), _code(dtype),
+    rc = _lib.load().cplxamd_iir_plan(int(n), int(order), int(sections), int(rows), int(filters), code(dtype),
                                       int(bool(cplx)), int(force), out)
     if rc == -3:
         raise CplxAmdError(f"iir: rows of {n} samples in {rows} rows exceed what the kernel indexes (2^40 samples, "
@@ -67,12 +67,47 @@ def _ct(dtype):
 
 
 def _call(xr, xi, cr, ci, zr, zi, yr, yi, fr, fi, runs, n, x_es, order, sections, segs, seg_len, flags, cx, dtype):
-    d = _lib.IirDesc(n=n, order=order, sections=sections, segments=segs, seg_len=seg_len, x_es=x_es, runs=len(runs),
-                     flags=flags)
-    for r, (size, sx, sc, sy) in enumerate(runs):
-        d.size[r], d.x_stride[r], d.c_stride[r], d.y_stride[r] = size, sx, sc, sy
+    d = _lib.IirDesc(n=n, order=order, sections=sections, segments=segs, seg_len=seg_len, x_es=x_es, flags=flags)
+    fill(d, runs, ("x_stride", "c_stride", "y_stride"))
     call("cplxamd_iir", ptr(xr), ptr(xi), ptr(cr), ptr(ci), ptr(zr), ptr(zi), ptr(yr), ptr(yi), ptr(fr), ptr(fi),
-         ctypes.byref(d), int(cx), _code(dtype), stream_ptr())
+         ctypes.byref(d), int(cx), code(dtype), stream_ptr())
+
+
+def split(launch, scan, plan_of, enter, x, y, runs, n, S, D, cx, ct, want_zf):
+    """The split path of one pass, for iir.py and filtfilt.py.  `runs`: the pass's batch runs, the coefficients' strides
+    in column 2; `plan_of(rows, filters)`: the caller's plan; `launch(x, z, y, f, runs, n, segs, seg_len)`: one launch of
+    the caller's primitive on plane pairs -- x of n samples a row ((None, None): null input), the entering states z, y
+    and the final states f; `scan`: the caller's module-level `call`; `enter()`: the row's entering state, planes of
+    [rows, S D] entries in the compute type `ct`, asked for when the scan needs it.
+    -> None, and nothing launched, where the rows stay whole: the plan says so, or the rows that share a filter are not
+    consecutive, or the filters do not fit two batch runs; else the four launches, and the final state planes
+    [rows, segs, S, D] of every segment ((None, None) unless `want_zf`)."""
+    kept = [r for r in runs if r[2] != 0]
+    rows, filters, w = math.prod(r[0] for r in runs), math.prod(r[0] for r in kept), S * D
+    p = plan_of(rows, filters)
+    segs, seg_len = p["segments"], p["seg_len"]
+    shared_inner = all(r[2] == 0 for r in runs[len(kept):]) and all(r[2] != 0 for r in runs[:len(kept)])
+    if segs == 1 or not (shared_inner and len(kept) <= 2):
+        return None
+    dev, none = x[0].device, (None, None)
+    new = lambda *s: (torch.empty(s, dtype=ct, device=dev), torch.empty(s, dtype=ct, device=dev) if cx else None)  # noqa: E731
+    # 1. segment-final states from zero entering state (in reverse time, segment 0 is the END of the row)
+    z = new(rows, segs, S, D)
+    launch(x, none, none, z, runs, n, segs, seg_len)
+    # 2. the transition of a full segment: unit entering states on null input, one row per (filter, unit state)
+    eye = torch.eye(w, dtype=ct, device=dev).reshape(1, w, 1, S, D).expand(filters, w, 1, S, D).contiguous()
+    m = new(filters * w, 1, S, D)
+    mruns = [[r[0], 0, r[2]] for r in kept] + [[w]]      # (the strides a run leaves out are zero)
+    launch(none, (eye, None), none, m, mruns, seg_len, 1, seg_len)
+    # 3. the entering state of every segment: a sequential scan per row
+    s = enter()
+    e = new(rows, segs, S, D)
+    scan("cplxamd_iir_scan", ptr(z[0]), ptr(z[1]), ptr(m[0]), ptr(m[1]), ptr(s[0]), ptr(s[1]), ptr(e[0]), ptr(e[1]), rows,
+         rows // max(filters, 1), segs, w, int(cx), code(ct), stream_ptr())
+    # 4. every segment from its true entering state; the last segment's final state is the row's
+    f = new(rows, segs, S, D) if want_zf else none
+    launch(x, e, y, f, runs, n, segs, seg_len)
+    return f
 
 
 def run(xr, xi, cr, ci, zr, zi, reverse=False, conj=False, cx=None, want_zf=False, force_segments=None):
@@ -90,56 +125,27 @@ def run(xr, xi, cr, ci, zr, zi, reverse=False, conj=False, cx=None, want_zf=Fals
     yr = torch.empty(shape, dtype=dtype, device=dev)
     yi = torch.empty_like(yr) if cx else None
     rows = math.prod(batch)
-    w = S * D
 
     def state(t):                                         # [rows, 1, S, D] in the compute type, dense
         return None if t is None else t.expand(batch + (S, D)).to(ct).reshape(rows, 1, S, D).contiguous()
 
-    xr, xi = _share(xr, xi)
-    flat = lambda t: None if t is None else t.reshape(tuple(t.shape[:-2]) + (S * W,))     # noqa: E731
-    joint = lambda: _runs(shape, (xr.stride(), _expanded_strides(flat(cr), batch + (S * W,)), _dense(shape)))  # noqa: E731
-    if len(joint()) > 3:
-        xr, xi = xr.contiguous(), None if xi is None else xi.contiguous()
-    if len(joint()) > 3:
-        cr, ci = cr.expand(batch + (S, W)).contiguous(), None if ci is None else ci.expand(batch + (S, W)).contiguous()
-    c2r, c2i = flat(cr), flat(ci)
-    runs = joint()
-    kept = [r for r in runs if r[2] != 0]
-    filters = math.prod(r[0] for r in kept)
-    p = plan(n, D, S, rows, filters, dtype, cx, force_segments)
-    segs, seg_len = p["segments"], p["seg_len"]
-    # the split path wants the rows that share a filter to be consecutive, and the filters to fit two batch runs
-    shared_inner = all(r[2] == 0 for r in runs[len(kept):]) and all(r[2] != 0 for r in runs[:len(kept)])
-    if segs > 1 and not (shared_inner and len(kept) <= 2):
-        segs, seg_len = 1, n
+    ((xr, xi), (cr, ci)), runs = fit(shape, [(xr, xi), (cr, ci)], dense(shape), [(0,), (1,)])
     flags = (_lib.IIR_REVERSE if reverse else 0) | (_lib.IIR_CONJ if conj else 0)
     zr, zi = state(zr), state(zi) if cx else None
-    new = lambda *s: torch.empty(s, dtype=ct, device=dev)  # noqa: E731
-    if segs == 1:
-        fr = new(rows, 1, S, D) if want_zf else None
-        fi = new(rows, 1, S, D) if want_zf and cx else None
-        _call(xr, xi, c2r, c2i, zr, zi, yr, yi, fr, fi, runs, n, xr.stride(-1), D, S, 1, n, flags, cx, dtype)
-    else:
-        # 1. segment-final states from zero entering state
-        z_r, z_i = new(rows, segs, S, D), new(rows, segs, S, D) if cx else None
-        _call(xr, xi, c2r, c2i, None, None, None, None, z_r, z_i, runs, n, xr.stride(-1), D, S, segs, seg_len, flags, cx, dtype)
-        # 2. the transition of a full segment: unit entering states on null input, one row per (filter, unit state)
-        eye = torch.eye(w, dtype=ct, device=dev).reshape(1, w, 1, S, D).expand(filters, w, 1, S, D).contiguous()
-        m_r, m_i = new(filters * w, 1, S, D), new(filters * w, 1, S, D) if cx else None
-        mruns = [[r[0], 0, r[2], 0] for r in kept] + [[w, 0, 0, 0]]
-        _call(None, None, c2r, c2i, eye, None, None, None, m_r, m_i, mruns, seg_len, 0, D, S, 1, seg_len, flags, cx, dtype)
-        # 3. the entering state of every segment: a sequential scan per row
-        e_r, e_i = new(rows, segs, S, D), new(rows, segs, S, D) if cx else None
-        call("cplxamd_iir_scan", ptr(z_r), ptr(z_i), ptr(m_r), ptr(m_i), ptr(zr), ptr(zi), ptr(e_r), ptr(e_i), rows,
-             rows // max(filters, 1), segs, w, int(cx), _code(ct), stream_ptr())
-        # 4. every segment from its true entering state; 5. the last segment's final state is zf
-        f_r, f_i = new(rows, segs, S, D), new(rows, segs, S, D) if cx else None
-        _call(xr, xi, c2r, c2i, e_r, e_i, yr, yi, f_r, f_i, runs, n, xr.stride(-1), D, S, segs, seg_len, flags, cx, dtype)
-        fr, fi = f_r[:, -1], None if f_i is None else f_i[:, -1]
+
+    def launch(x, z, y, f, runs, n, segs, seg_len):
+        _call(*x, cr, ci, *z, *y, *f, runs, n, 0 if x[0] is None else xr.stride(-1), D, S, segs, seg_len, flags, cx, dtype)
+
+    f = split(launch, call, lambda r, k: plan(n, D, S, r, k, dtype, cx, force_segments), lambda: (zr, zi), (xr, xi), (yr, yi),
+              runs, n, S, D, cx, ct, True)
+    if f is None:
+        f = (torch.empty(rows, 1, S, D, dtype=ct, device=dev) if want_zf else None,
+             torch.empty(rows, 1, S, D, dtype=ct, device=dev) if want_zf and cx else None)
+        launch((xr, xi), (zr, zi), (yr, yi), f, runs, n, 1, n)
     if not want_zf:
         return yr, yi, None, None
-    back = lambda t: None if t is None else t.reshape(batch + (S, D)).to(dtype)  # noqa: E731
-    return yr, yi, back(fr), back(fi)
+    back = lambda t: None if t is None else t[:, -1].reshape(batch + (S, D)).to(dtype)  # noqa: E731
+    return yr, yi, back(f[0]), back(f[1])
 
 
 def _conj_planes(pr, pi, flip):
@@ -212,24 +218,16 @@ class _Iir(torch.autograd.Function):
 def filt(xr, xi, cr, ci, zr, zi, reverse=False, conj=False, cx=None):
     """The primitive on planes, differentiable to any order: x [*B, N] (views welcome), c [*Bc, S, 2 (D + 1)] with Bc
     broadcastable to B and as many dims, z [*B, S, D] or None -> (yr, yi), yi None when every operand is real."""
-    xr, xi = _share(xr, xi)
-    cr, ci = _share(cr, ci)
+    xr, xi = share(xr, xi)
+    cr, ci = share(cr, ci)
     if zr is not None:
-        zr, zi = _share(zr, zi)
-    S, W = cr.shape[-2], cr.shape[-1]
-    if cr.stride()[-2:] != (W, 1) and cr.numel():
+        zr, zi = share(zr, zi)
+    if cr.stride()[-2:] != (cr.shape[-1], 1) and cr.numel():
         cr, ci = cr.contiguous(), None if ci is None else ci.contiguous()
     if cx is None:
         cx = xi is not None or ci is not None or (zr is not None and zi is not None)
     shape = tuple(xr.shape)
-    cshape = shape[:-1] + (S * W,)
-    strides = lambda: (xr.stride(), _expanded_strides(cr.reshape(tuple(cr.shape[:-2]) + (S * W,)), cshape),  # noqa: E731
-                       _dense(shape))
-    if len(_runs(shape, strides())) > 3:
-        xr, xi = xr.contiguous(), None if xi is None else xi.contiguous()     # one differentiable copy
-    if len(_runs(shape, strides())) > 3:
-        full = shape[:-1] + (S, W)
-        cr, ci = cr.expand(full).contiguous(), None if ci is None else ci.expand(full).contiguous()
+    ((xr, xi), (cr, ci)), _ = fit(shape, [(xr, xi), (cr, ci)], dense(shape), [(0,), (1,)])   # copies: x, then c expanded
     return _Iir.apply(xr, xi, cr, ci, zr, zi, (bool(reverse), bool(conj), bool(cx)))
 
 
@@ -310,13 +308,12 @@ def _section(xr, xi, cr, ci, zr, zi, D, cx):
 
 def _operands(fn, named):
     """planes of every operand, with the checks the two functions share -> {name: (re, im)}"""
-    from .upfirdn import _planes
     out, first = {}, None
     for name, v in named:
         if v is None:
             out[name] = (None, None)
             continue
-        pr, pi = _planes(v, name, fn)
+        pr, pi = planes(v, name, fn)
         if pr.dim() == 0:
             raise ValueError(f"{fn}: `{name}` is 0-d: there is no dim to filter along")
         if first is None:
@@ -324,7 +321,7 @@ def _operands(fn, named):
         elif pr.dtype != first[1]:
             raise CplxAmdError(f"{fn}: the operands have different dtypes: `{first[0]}` is {first[1]}, `{name}` is {pr.dtype}")
         out[name] = (pr, pi)
-    _code(first[1])
+    code(first[1])
     return out
 
 

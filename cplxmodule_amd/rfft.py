@@ -11,7 +11,7 @@ C2R is R2C with the opposite sign, weighted exactly when c = w.  Each backward i
 every order exist.  The adjoint of zero padding is `narrow`; truncation is a view.
 
 One launch of `cplxamd_rfft` transforms every vector along ONE dim, reading the planes where they lie (runs and layouts
-as cplxmodule_amd/fft.py; one differentiable copy only when planes share no layout or need more than three runs).  The
+as cplxmodule_amd/fft.py, by _runs.py's rule; one differentiable copy only when planes share no layout or need more than three runs).  The
 output is dense in the input's memory order.  rfftn is the R2C launch along the LAST listed dim, then fft.py's complex
 launches over the others; irfftn the complex inverses first, the C2R launch last; for bf16 the intermediates are float32
 and the result is rounded once.  The workspace comes from torch's allocator, no device value is read on the host.
@@ -22,7 +22,8 @@ import torch
 
 from . import _lib
 from ._lib import CplxAmdError, call, ptr, require_device, stream_ptr
-from .fft import MAX_N, PATHS, _arguments, _code, _dense_like, _runs, _scale, transform
+from ._runs import code, fill, fit_like
+from .fft import MAX_N, PATHS, _arguments, _scale, transform
 
 FLAG_INVERSE, FLAG_C2R, FLAG_WEIGHTED = 1, 4, 8                       # CPLXAMD_FFT_INVERSE, CPLXAMD_RFFT_C2R, CPLXAMD_RFFT_WEIGHTED
 
@@ -31,21 +32,19 @@ def plan(n, vectors, dtype=torch.float32, c2r=False):
     """(path, length of the complex transform, points actually run, vectors per workgroup, workspace bytes) of a real
     transform of length n -- a pure host call, no GPU needed.  Even n runs n / 2 complex points."""
     cn, pts, vpw, ws = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int64(0)
-    rc = _lib.load().cplxamd_rfft_plan(int(n), int(vectors), _code(dtype), int(bool(c2r)), ctypes.byref(cn), ctypes.byref(pts),
+    rc = _lib.load().cplxamd_rfft_plan(int(n), int(vectors), code(dtype), int(bool(c2r)), ctypes.byref(cn), ctypes.byref(pts),
                                        ctypes.byref(vpw), ctypes.byref(ws))
     if rc < 0:
         raise CplxAmdError(f"rfft: transform length {n} is outside [1, 2^22 = {MAX_N}], the lengths the kernels support")
     return PATHS[rc], cn.value, pts.value, vpw.value, ws.value
 
 
-def _launch(xr, xi, yr, yi, n, n_in, dim, flags, scale, c2r):
-    runs = _runs(yr.shape, xr.stride(), yr.stride(), dim)
-    d = _lib.FftDesc(n=n, n_in=n_in, x_es=xr.stride(dim), y_es=yr.stride(dim), runs=len(runs), inverse=flags, scale=scale)
-    for r, (size, xs, ys) in enumerate(runs):
-        d.size[r], d.x_stride[r], d.y_stride[r] = size, xs, ys
-    ws_bytes = plan(n, yr.numel() // yr.shape[dim], xr.dtype, c2r)[4]
+def _launch(xr, xi, yr, yi, n, n_in, dim, flags, scale, c2r, batch):
+    d = _lib.FftDesc(n=n, n_in=n_in, x_es=xr.stride(dim), y_es=yr.stride(dim), inverse=flags, scale=scale)
+    vectors, _ = fill(d, batch, ("x_stride", "y_stride"))
+    ws_bytes = plan(n, vectors, xr.dtype, c2r)[4]
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xr.device)
-    call("cplxamd_rfft", ptr(xr), ptr(xi), ptr(yr), ptr(yi), ctypes.byref(d), _code(xr.dtype), _code(yr.dtype), ptr(ws),
+    call("cplxamd_rfft", ptr(xr), ptr(xi), ptr(yr), ptr(yi), ctypes.byref(d), code(xr.dtype), code(yr.dtype), ptr(ws),
          ws_bytes, stream_ptr())
 
 
@@ -55,19 +54,19 @@ class _R2C(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, meta):
-        n, dim, positive, weighted, scale, out_dtype = meta
-        ctx.meta = meta
+        n, dim, positive, weighted, scale, out_dtype, batch, ys = meta
+        ctx.meta = meta[:5]
         ctx.src = (x.shape[dim], x.dtype)
-        yr = torch.empty_strided(*_dense_like(x, dim, n // 2 + 1), dtype=out_dtype, device=x.device)
+        yr = torch.empty_strided(x.shape[:dim] + (n // 2 + 1,) + x.shape[dim + 1:], ys, dtype=out_dtype, device=x.device)
         yi = torch.empty_like(yr)
         if yr.numel():
             _launch(x, None, yr, yi, n, min(n, x.shape[dim]), dim, (FLAG_INVERSE if positive else 0) | (FLAG_WEIGHTED if weighted else 0),
-                    scale, False)
+                    scale, False, batch)
         return yr, yi
 
     @staticmethod
     def backward(ctx, gr, gi):
-        n, dim, positive, weighted, scale, _ = ctx.meta
+        n, dim, positive, weighted, scale = ctx.meta
         extent, dtype = ctx.src
         dx = c2r(gr, gi, n, dim, not positive, weighted, scale, dtype)
         return (dx.narrow(dim, 0, extent) if extent < n else dx), None
@@ -79,18 +78,18 @@ class _C2R(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pr, pi, meta):
-        n, dim, positive, weighted, scale, out_dtype = meta
-        ctx.meta = meta
+        n, dim, positive, weighted, scale, out_dtype, batch, ys = meta
+        ctx.meta = meta[:5]
         ctx.src = (pr.shape[dim], pr.dtype)
-        y = torch.empty_strided(*_dense_like(pr, dim, n), dtype=out_dtype, device=pr.device)
+        y = torch.empty_strided(pr.shape[:dim] + (n,) + pr.shape[dim + 1:], ys, dtype=out_dtype, device=pr.device)
         if y.numel():
             _launch(pr, pi, y, None, n, pr.shape[dim], dim, FLAG_C2R | (FLAG_INVERSE if positive else 0) | (FLAG_WEIGHTED if weighted else 0),
-                    scale, True)
+                    scale, True, batch)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        n, dim, positive, weighted, scale, _ = ctx.meta
+        n, dim, positive, weighted, scale = ctx.meta
         extent, dtype = ctx.src
         dr, di = r2c(g, n, dim, not positive, weighted, scale, dtype)
         if extent < n // 2 + 1:                           # the adjoint of zero padding
@@ -102,9 +101,8 @@ def r2c(x, n, dim, positive, weighted, scale, out_dtype):
     """the R2C primitive along `dim` (non-negative) of a real tensor -> planes of `out_dtype` with n // 2 + 1 entries"""
     if x.shape[dim] > n:                                  # truncation: a view (autograd pads its gradient)
         x = x.narrow(dim, 0, n)
-    if len(_runs(x.shape, x.stride(), _dense_like(x, dim, n // 2 + 1)[1], dim)) > 3:
-        x = x.contiguous()                                # one differentiable copy
-    return _R2C.apply(x, (n, dim, bool(positive), bool(weighted), float(scale), out_dtype))
+    x, _, batch, ys = fit_like(x, None, dim, n // 2 + 1)  # at most one differentiable copy
+    return _R2C.apply(x, (n, dim, bool(positive), bool(weighted), float(scale), out_dtype, batch, ys))
 
 
 def c2r(pr, pi, n, dim, positive, weighted, scale, out_dtype):
@@ -112,9 +110,8 @@ def c2r(pr, pi, n, dim, positive, weighted, scale, out_dtype):
     n entries; the first n // 2 + 1 entries are used"""
     if pr.shape[dim] > n // 2 + 1:
         pr, pi = pr.narrow(dim, 0, n // 2 + 1), pi.narrow(dim, 0, n // 2 + 1)
-    if pr.stride() != pi.stride() or len(_runs(pr.shape, pr.stride(), _dense_like(pr, dim, n)[1], dim)) > 3:
-        pr, pi = pr.contiguous(), pi.contiguous()         # one differentiable copy
-    return _C2R.apply(pr, pi, (n, dim, bool(positive), bool(weighted), float(scale), out_dtype))
+    pr, pi, batch, ys = fit_like(pr, pi, dim, n)          # at most one differentiable copy
+    return _C2R.apply(pr, pi, (n, dim, bool(positive), bool(weighted), float(scale), out_dtype, batch, ys))
 
 
 def arguments(input, s, dim, norm, name, real_out):
@@ -161,7 +158,7 @@ def rfftn(input, s, dim, norm, positive, name):
         raise CplxAmdError(f"{name}: the input is a {type(input).__name__}"
                            f"{' of complex dtype' if torch.is_tensor(input) else ''}, not a real torch.Tensor")
     todo = arguments(input, s, dim, norm, name, False)
-    _code(input.dtype)
+    code(input.dtype)
     _check_lengths(todo, name)
     require_device(input)
     wide = torch.float32 if input.dtype == torch.bfloat16 else input.dtype
@@ -184,7 +181,7 @@ def irfftn(input, s, dim, norm, positive, name):
     pr, pi = input.real, input.imag
     if pr.dtype != pi.dtype:
         raise CplxAmdError(f"{name}: the planes have different dtypes: {pr.dtype} and {pi.dtype}")
-    _code(pr.dtype)
+    code(pr.dtype)
     _check_lengths(todo, name)
     require_device(pr, pi)
     dtype = pr.dtype

@@ -34,7 +34,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import CplxAmdError, call, ptr, require_device, stream_ptr
-from .fft import MAX_N, PATHS, _code
+from ._runs import code
+from .fft import MAX_N, PATHS
 
 FLAG_INVERSE, FLAG_WEIGHTED, FLAG_FULL = 1, 8, 16         # CPLXAMD_FFT_INVERSE, CPLXAMD_RFFT_WEIGHTED, CPLXAMD_STFT_FULL
 PAD_ZERO, PAD_REFLECT = 0, 1                              # CPLXAMD_STFT_PAD_*
@@ -47,7 +48,7 @@ def plan(n_fft, hop, padded_length, rows, length, dtype=torch.float32, full=Fals
     host call, no GPU needed.  `full`: the full spectrum on the complex transform of n_fft points."""
     cn, pts, fr, chunk, wa, wsyn = (ctypes.c_int64(0) for _ in range(6))
     vpw = ctypes.c_int(0)
-    rc = _lib.load().cplxamd_stft_plan(int(n_fft), int(hop), int(padded_length), int(rows), int(length), _code(dtype), int(bool(full)),
+    rc = _lib.load().cplxamd_stft_plan(int(n_fft), int(hop), int(padded_length), int(rows), int(length), code(dtype), int(bool(full)),
                                        ctypes.byref(cn), ctypes.byref(pts), ctypes.byref(vpw), ctypes.byref(fr),
                                        ctypes.byref(chunk), ctypes.byref(wa), ctypes.byref(wsyn))
     if rc < 0:
@@ -119,7 +120,7 @@ class _Analysis(torch.autograd.Function):
                               sig_imag=None if xi is None else xi.data_ptr(), scale=scale)
             ws_bytes = plan(n_fft, hop, (frames - 1) * hop + n_fft, rows, x.shape[-1], x.dtype, full)["analysis_ws"]
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-            call("cplxamd_stft", ptr(x), ptr(yr), ptr(yi), ctypes.byref(d), _code(x.dtype), ptr(ws), ws_bytes, stream_ptr())
+            call("cplxamd_stft", ptr(x), ptr(yr), ptr(yi), ctypes.byref(d), code(x.dtype), ptr(ws), ws_bytes, stream_ptr())
         return yr.transpose(-1, -2), yi.transpose(-1, -2)
 
     @staticmethod
@@ -152,7 +153,7 @@ class _Synthesis(torch.autograd.Function):
                               scale=scale)
             ws_bytes = plan(n_fft, hop, (pr.shape[-1] - 1) * hop + n_fft, rows, length, pr.dtype, full)["synthesis_ws"]
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pr.device)
-            call("cplxamd_istft", ptr(pr), ptr(pi), ptr(y), ctypes.byref(d), _code(pr.dtype), ptr(ws), ws_bytes, stream_ptr())
+            call("cplxamd_istft", ptr(pr), ptr(pi), ptr(y), ctypes.byref(d), code(pr.dtype), ptr(ws), ws_bytes, stream_ptr())
         return (y, yi) if imag else y
 
     @staticmethod
@@ -263,7 +264,7 @@ def stft(input, n_fft, hop_length=None, win_length=None, window=None, center=Tru
     onesided = (not is_cplx) if onesided is None else bool(onesided)
     if is_cplx and input.real.dtype != input.imag.dtype:
         raise CplxAmdError(f"stft: the planes have different dtypes: {input.real.dtype} and {input.imag.dtype}")
-    _code(x.dtype)
+    code(x.dtype)
     if n_fft > MAX_N:
         raise CplxAmdError(f"stft: length {n_fft} exceeds 2^22 = {MAX_N}, the longest transform supported")
     xi = input.imag if is_cplx else None
@@ -316,7 +317,7 @@ def istft(input, n_fft, hop_length=None, win_length=None, window=None, center=Tr
         raise RuntimeError(f"istft: the frames cover no output sample (output length {out_length})")
     if pr.dtype != pi.dtype:
         raise CplxAmdError(f"istft: the planes have different dtypes: {pr.dtype} and {pi.dtype}")
-    _code(pr.dtype)
+    code(pr.dtype)
     if n_fft > MAX_N:
         raise CplxAmdError(f"istft: length {n_fft} exceeds 2^22 = {MAX_N}, the longest transform supported")
     require_device(pr, pi, window)

@@ -13,7 +13,7 @@ so derivatives of every order stay on the two kernels, and no pass flips, conjug
 A real operand is a null imaginary plane (never read, no zero plane allocated; the kernels are compiled per operand
 pair); the gradient of a real operand is the real part (the null output plane is not stored).
 
-Leading dims broadcast by torch's rules and are read where they lie, under fftconv.py's rule: at most three batch runs
+Leading dims broadcast by torch's rules and are read where they lie, under _runs.py's rule: at most three batch runs
 jointly for both operands and the result, otherwise one differentiable copy.  The weight gradient's workspace comes from
 torch's allocator and nothing reads a device value on the host: calls can be captured in a hipGraph.
 
@@ -28,8 +28,7 @@ import torch
 
 from . import _lib
 from ._lib import CplxAmdError, call, ptr, require_device, stream_ptr
-from .fft import _code
-from .fftconv import _dense, _expanded_strides, _runs, _share
+from ._runs import code, dense, fill, fit, fit_wgrad, planes
 
 PATHS = ("fused", "composed")                              # cplxamd_upfirdn_plan's return codes
 FUSED_MAX_K = 4096
@@ -42,7 +41,7 @@ def plan(a_len, k, c_len, up=1, down=1, off=0, rows=1, filters=1, dtype=torch.fl
     gradient's tile, tap blocks, chunks and workspace bytes)."""
     out = (ctypes.c_int64 * len(_lib.UPFIRDN_PLAN_FIELDS))()
     rc = _lib.load().cplxamd_upfirdn_plan(int(a_len), int(k), int(c_len), int(up), int(down), int(off), int(rows), int(filters),
-                                          _code(dtype), int(bool(conj)), int(bool(a_cplx)), int(bool(b_cplx)), out)
+                                          code(dtype), int(bool(conj)), int(bool(a_cplx)), int(bool(b_cplx)), out)
     if rc == -3:
         raise CplxAmdError(f"upfirdn: lengths {a_len}, {k}, {c_len} at rates {up}/{down} and offset {off} exceed what the "
                            "kernels index (rates up to 2^30, lengths up to 2^40, 2^31 - 1 workgroups)")
@@ -53,19 +52,12 @@ def plan(a_len, k, c_len, up=1, down=1, off=0, rows=1, filters=1, dtype=torch.fl
     return p
 
 
-def _launch(name, ar, ai, br, bi, yr, yi, shape, y_strides, a_len, k, c_len, up, down, off, conj, wgrad):
-    """one call of cplxamd_upfirdn / _wgrad over the batch `shape[:-1]`; b is read with its broadcast strides"""
-    sa, sb = ar.stride(), _expanded_strides(br, shape[:-1] + (br.shape[-1],))
-    runs = _runs(shape, (sa, sb, y_strides))
-    d = _lib.UpfirdnDesc(a_len=a_len, k=k, c_len=c_len, up=up, down=down, off=off, a_es=sa[-1], b_es=sb[-1], runs=len(runs),
+def _launch(name, ar, ai, br, bi, yr, yi, runs, a_len, k, c_len, up, down, off, conj, wgrad):
+    """one call of cplxamd_upfirdn / _wgrad over the batch runs of (a, b, y); b is read with its broadcast strides"""
+    d = _lib.UpfirdnDesc(a_len=a_len, k=k, c_len=c_len, up=up, down=down, off=off, a_es=ar.stride(-1), b_es=br.stride(-1),
                          conj=int(conj))
-    rows, filters = 1, 1
-    for r, (size, xa, xb, xy) in enumerate(runs):
-        d.size[r], d.a_stride[r], d.b_stride[r], d.y_stride[r] = size, xa, xb, xy
-        rows *= size
-        if (xy if wgrad else xb) != 0:
-            filters *= size
-    args = (ptr(ar), ptr(ai), ptr(br), ptr(bi), ptr(yr), ptr(yi), ctypes.byref(d), _code(ar.dtype))
+    rows, filters = fill(d, runs, ("a_stride", "b_stride", "y_stride"), "y_stride" if wgrad else "b_stride")
+    args = (ptr(ar), ptr(ai), ptr(br), ptr(bi), ptr(yr), ptr(yi), ctypes.byref(d), code(ar.dtype))
     if not wgrad:
         return call(name, *args, stream_ptr())
     ws_bytes = plan(a_len, k, c_len, up, down, off, rows, filters, ar.dtype, False, ai is not None,
@@ -80,15 +72,14 @@ class _P1(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xr, xi, hr, hi, meta):
-        up, down, off, length, conj, out_imag = meta
-        ctx.meta = meta
+        up, down, off, length, conj, out_imag, runs = meta
+        ctx.meta = meta[:6]
         ctx.save_for_backward(xr, xi, hr, hi)
-        shape = tuple(xr.shape[:-1]) + (length,)
-        yr = torch.empty(shape, dtype=xr.dtype, device=xr.device)
+        yr = torch.empty(tuple(xr.shape[:-1]) + (length,), dtype=xr.dtype, device=xr.device)
         yi = torch.empty_like(yr) if out_imag else None
         if yr.numel():
-            _launch("cplxamd_upfirdn", xr, xi, hr, hi, yr, yi, shape, yr.stride(), xr.shape[-1], hr.shape[-1], length, up, down,
-                    off, conj, False)
+            _launch("cplxamd_upfirdn", xr, xi, hr, hi, yr, yi, runs, xr.shape[-1], hr.shape[-1], length, up, down, off, conj,
+                    False)
         return yr, yi
 
     @staticmethod
@@ -111,15 +102,14 @@ class _P2(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ar, ai, cr, ci, meta):
-        up, down, off, k, fshape, out_imag = meta
-        ctx.meta = meta
+        up, down, off, k, fshape, out_imag, runs = meta
+        ctx.meta = meta[:6]
         ctx.save_for_backward(ar, ai, cr, ci)
         yr = torch.empty(fshape + (k,), dtype=ar.dtype, device=ar.device)
         yi = torch.empty_like(yr) if out_imag else None
-        shape = tuple(ar.shape[:-1]) + (k,)
         if yr.numel() and ar.numel():
-            _launch("cplxamd_upfirdn_wgrad", ar, ai, cr, ci, yr, yi, shape, _expanded_strides(yr, shape), ar.shape[-1], k,
-                    cr.shape[-1], up, down, off, False, True)
+            _launch("cplxamd_upfirdn_wgrad", ar, ai, cr, ci, yr, yi, runs, ar.shape[-1], k, cr.shape[-1], up, down, off, False,
+                    True)
         elif yr.numel():                                  # no rows to sum
             yr.zero_()
             if yi is not None:
@@ -142,51 +132,20 @@ class _P2(torch.autograd.Function):
 def conv(xr, xi, hr, hi, up, down, off, length, conj=False, out_imag=True):
     """P1 on planes: x [*B, N] (views welcome), filter h [*Bh, K] with Bh broadcastable to B and as many dims -> (yr, yi)
     of [*B, length], yi None unless `out_imag`.  Differentiable to any order."""
-    xr, xi = _share(xr, xi)
-    hr, hi = _share(hr, hi)
     shape = tuple(xr.shape[:-1]) + (length,)
-    fshape = shape[:-1] + (hr.shape[-1],)
-    if len(_runs(shape, (xr.stride(), _expanded_strides(hr, fshape), _dense(shape)))) > 3:
-        xr, xi = xr.contiguous(), None if xi is None else xi.contiguous()     # one differentiable copy
-    if len(_runs(shape, (xr.stride(), _expanded_strides(hr, fshape), _dense(shape)))) > 3:
-        hr, hi = hr.expand(fshape).contiguous(), None if hi is None else hi.expand(fshape).contiguous()
-    return _P1.apply(xr, xi, hr, hi, (int(up), int(down), int(off), int(length), bool(conj), bool(out_imag)))
+    ((xr, xi), (hr, hi)), runs = fit(shape, [(xr, xi), (hr, hi)], dense(shape), [(0,), (1,)])     # copies: x, then h expanded
+    return _P1.apply(xr, xi, hr, hi, (int(up), int(down), int(off), int(length), bool(conj), bool(out_imag), runs))
 
 
 def wgrad(ar, ai, cr, ci, up, down, off, k, fshape, out_imag=True):
     """P2 on planes: a [*B, A], c [*B, C] -> (yr, yi) of [*fshape, k] (fshape broadcastable to B, as many dims): the
     rows that fshape broadcasts over are summed inside the kernel.  Differentiable to any order."""
-    ar, ai = _share(ar, ai)
-    cr, ci = _share(cr, ci)
-    batch = tuple(ar.shape[:-1])
-    shape = batch + (k,)
-
-    def too_many(f):
-        ys = torch.empty(tuple(f) + (k,), device="meta").expand(shape).stride()
-        return len(_runs(shape, (ar.stride(), cr.stride(), ys))) > 3
-
-    if too_many(fshape):
-        ar, ai = ar.contiguous(), None if ai is None else ai.contiguous()     # one differentiable copy each
-        cr, ci = cr.contiguous(), None if ci is None else ci.contiguous()
-    meta = (int(up), int(down), int(off), int(k))
-    if too_many(fshape):                                  # the broadcast pattern itself: per-row results, summed by torch
-        yr, yi = _P2.apply(ar, ai, cr, ci, meta + (batch, bool(out_imag)))
-        to = tuple(fshape) + (k,)
-        return yr.sum_to_size(to), None if yi is None else yi.sum_to_size(to)
-    return _P2.apply(ar, ai, cr, ci, meta + (tuple(fshape), bool(out_imag)))
-
-
-def _planes(x, name, fn):
-    from .cplx import Cplx
-    if isinstance(x, Cplx):
-        pr, pi = x.real, x.imag
-        if pr.dtype != pi.dtype:
-            raise CplxAmdError(f"{fn}: the planes of `{name}` have different dtypes: {pr.dtype} and {pi.dtype}")
-        return pr, pi
-    if torch.is_tensor(x) and not x.is_complex():
-        return x, None
-    raise CplxAmdError(f"{fn}: `{name}` is a {type(x).__name__}{' of complex dtype' if torch.is_tensor(x) else ''}, "
-                       "not a Cplx or a real torch.Tensor (wrap planes with Cplx(re, im); torch complex tensors are not taken)")
+    (ar, ai), (cr, ci), runs, f = fit_wgrad((ar, ai), (cr, ci), k, fshape)
+    yr, yi = _P2.apply(ar, ai, cr, ci, (int(up), int(down), int(off), int(k), f, bool(out_imag), runs))
+    if f == tuple(fshape):
+        return yr, yi
+    to = tuple(fshape) + (k,)                             # the broadcast pattern itself: per-row results, summed by torch
+    return yr.sum_to_size(to), None if yi is None else yi.sum_to_size(to)
 
 
 def _composed(xr, xi, hr, hi, up, down, off, length):
@@ -216,7 +175,7 @@ def _composed(xr, xi, hr, hi, up, down, off, length):
 def _rate_change(fn, x, h, up, down, off, length_of):
     """the shared body of upfirdn and resample_poly: y[n] = sum_k h[k] xu[n down + off - k], n < length_of(N, K)"""
     from .cplx import Cplx
-    (xr, xi), (hr, hi) = _planes(x, "x", fn), _planes(h, "h", fn)
+    (xr, xi), (hr, hi) = planes(x, "x", fn), planes(h, "h", fn)
     for t, name in ((xr, "x"), (hr, "h")):
         if t.dim() == 0:
             raise ValueError(f"{fn}: `{name}` is 0-d: there is no dim to filter along")
@@ -225,7 +184,7 @@ def _rate_change(fn, x, h, up, down, off, length_of):
     batch = tuple(torch.broadcast_shapes(xr.shape[:-1], hr.shape[:-1]))       # RuntimeError, as torch raises it
     if xr.dtype != hr.dtype:
         raise CplxAmdError(f"{fn}: the operands have different dtypes: {xr.dtype} and {hr.dtype}")
-    _code(xr.dtype)
+    code(xr.dtype)
     n, k = xr.shape[-1], hr.shape[-1]
     length = length_of(n, k)
     path = plan(n, k, length, up, down, off, 1, 1, xr.dtype, False, xi is not None, hi is not None)["path"]
@@ -281,7 +240,7 @@ def resample_poly(x, up, down, window=("kaiser", 5.0)):
         h = None
     else:
         raise ValueError(f"resample_poly: window must be ('kaiser', beta) or a 1-d tensor of taps, got {window!r}")
-    xr, xi = _planes(x, "x", "resample_poly")
+    xr, xi = planes(x, "x", "resample_poly")
     if up == down:                                        # the input, as scipy returns a copy of it
         return xr.clone() if xi is None else type(x)(xr.clone(), xi.clone())
     if h is None:
