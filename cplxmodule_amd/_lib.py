@@ -445,6 +445,11 @@ _ERRORS = {-1: "invalid argument", -2: "misaligned pointer / leading dimension",
            -3: "unsupported shape", -4: "workspace too small"}
 
 
+def _raise(name, rc):
+    what = _ERRORS.get(rc, f"hipError_t {rc}" if rc > 0 else f"error {rc}")
+    raise CplxAmdError(f"{name} failed: {what}")
+
+
 def try_call(name, *args):
     """Like `call`, but returns False when the entry point declines the shape
     (CPLXAMD_ESHAPE = "use the generic kernel"); every other failure raises."""
@@ -452,8 +457,7 @@ def try_call(name, *args):
     if rc == -3:
         return False
     if rc != 0:
-        what = _ERRORS.get(rc, f"hipError_t {rc}" if rc > 0 else f"error {rc}")
-        raise CplxAmdError(f"{name} failed: {what}")
+        _raise(name, rc)
     return True
 
 
@@ -461,8 +465,7 @@ def call(name, *args):
     """Invoke an entry point; non-zero return codes become exceptions."""
     rc = getattr(load(), name)(*args)
     if rc != 0:
-        what = _ERRORS.get(rc, f"hipError_t {rc}" if rc > 0 else f"error {rc}")
-        raise CplxAmdError(f"{name} failed: {what}")
+        _raise(name, rc)
 
 
 _empty_anchor = {}
@@ -504,9 +507,46 @@ def scratch_key(device):
     """Key of the per-(device, stream) scratch caches (split-K slabs, BN / KL partial sums, conv slabs): kernels
     launched on two streams must not share a workspace.  During hipGraph capture the capturing stream's key is
     used like any other, so a cache grown inside a capture belongs to that capture's pool only."""
-    dev = torch.device(device)
+    dev = device if isinstance(device, torch.device) else torch.device(device)     # (a tensor's .device: nothing is built)
+    if dev.type != "cuda":
+        return (dev.type, dev.index, 0)
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    return (dev.type, idx, _current_stream_handle(idx) if dev.type == "cuda" else 0)
+    return (dev.type, idx, _current_stream_handle(idx))
+
+
+_scratch = {}       # (tag, scratch_key) -> uint8 buffer
+
+
+def scratch(tag, device, nbytes, floor=0):
+    """THE per-(device, stream) scratch workspace: a uint8 buffer of at least `nbytes`, kept per `tag` and
+    `scratch_key(device)` and replaced by a larger one (never below `floor` bytes) only when a request outgrows it.
+    Tags are separate buffers -- two can be live in one launch (split-K slab + 3M workspace, conv slab + column sums)."""
+    key = (tag, scratch_key(device))
+    buf = _scratch.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = _scratch[key] = torch.empty(max(nbytes, floor), dtype=torch.uint8, device=device)
+    return buf
+
+
+def al16(t):
+    """The streaming kernels move 16 bytes per lane: re-home the rare view that is not aligned (None passes)."""
+    return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
+
+
+def ntuple(v, n):
+    """`v` n times unless it is a sequence already (stride, padding, dilation, kernel size)."""
+    return (v,) * n if isinstance(v, int) else tuple(v)
+
+
+def plane_code(what, dtype):
+    """ABI dtype code of the float64-capable entry points (transforms, spectra); `what` opens the error message."""
+    if dtype == torch.float32:
+        return F32
+    if dtype == torch.bfloat16:
+        return BF16
+    if dtype == torch.float64:
+        return F64
+    raise CplxAmdError(f"{what}, got {dtype}")
 
 
 def dtype_code(t):

@@ -7,22 +7,15 @@ A descriptor holds at most MAX_RUNS of them (csrc/runs.h decodes them).  Operand
 differentiably, in an order each caller fixes (`fit`; `fit_like` for the one operand of a transform, `fit_wgrad` for a
 weight gradient); `fill` writes the runs into a ctypes descriptor.
 """
+import functools
+
 import torch
 
 from . import _lib
 from ._lib import CplxAmdError
 
 MAX_RUNS = 3
-
-
-def code(dtype):
-    if dtype == torch.float32:
-        return _lib.F32
-    if dtype == torch.bfloat16:
-        return _lib.BF16
-    if dtype == torch.float64:
-        return _lib.F64
-    raise CplxAmdError(f"fft: planes must be float32, bfloat16 or float64, got {dtype}")
+code = functools.partial(_lib.plane_code, "fft: planes must be float32, bfloat16 or float64")
 
 
 def planes(x, name, fn):

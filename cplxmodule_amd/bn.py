@@ -3,24 +3,12 @@ import torch
 
 from . import _lib, ops
 from .ops import once_differentiable
-from ._lib import call, dtype_code, ptr, require_device, stream_ptr, scratch_key
-
-_ws_cache = {}
-
-
-def _al16(t):
-    """The vectorised reduce / apply kernels issue 16-byte accesses: re-home the rare contiguous view that
-    does not start on a 16-byte boundary."""
-    return t if t.data_ptr() % 16 == 0 else t.clone()
+from ._lib import call, dtype_code, ptr, require_device, stream_ptr, scratch
+from ._lib import al16 as _al16      # (the vectorised reduce / apply kernels issue 16-byte accesses)
 
 
 def _ws(device, F):
-    need = int(_lib.load().cplxamd_bn_ws_bytes(F))
-    key = scratch_key(device)
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < need:
-        buf = _ws_cache[key] = torch.empty(need, dtype=torch.uint8, device=device)
-    return buf
+    return scratch("bn", device, int(_lib.load().cplxamd_bn_ws_bytes(F)))
 
 
 def _geom(x):

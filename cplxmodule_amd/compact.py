@@ -433,7 +433,7 @@ def conv2d(layer, input, plan):
     x = GatherFn.apply(xr, xi, plan.cols, plan.inv_cols, 1)
     wc = CompactWeightFn.apply(wr, wi, mask, plan, _weight_dtype(wr, xr))
     if plan.empty:
-        shape, padding = list(xr.shape), conv._pair(layer.padding)
+        shape, padding = list(xr.shape), conv.ntuple(layer.padding, 2)
         if layer.padding_mode == "circular":
             # cplx_conv2d pads, then convolves unpadded; conv._circular_pad hands `padding` to F.pad, which starts at the
             # LAST dimension: padding[0] widens W and padding[1] widens H (the reference's order)

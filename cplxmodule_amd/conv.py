@@ -13,20 +13,24 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .ops import once_differentiable
-from ._lib import CplxAmdError, call, try_call, dtype_code, launch_flags, ptr, require_device, stream_ptr
+from ._lib import CplxAmdError, call, try_call, dtype_code, launch_flags, ntuple, ptr, require_device, stream_ptr
 from .cplx import Cplx
-
-_ws_cache = {}
 
 
 def _pair(v):
-    return (v, v) if isinstance(v, int) else tuple(v)
+    """_lib.ntuple(v, 2) under the name the suite computes its reference geometry with (tests/test_gpu_r03.py)."""
+    return ntuple(v, 2)
+
+
+def is_planar(t):
+    """Stored plain contiguous (NCHW) and not channels-last as well (C == 1 or H * W == 1 is both)."""
+    return t.is_contiguous() and not t.is_contiguous(memory_format=torch.channels_last)
 
 
 def _geom(x_shape, w_shape, stride, padding, dilation, groups):
     B, Ci, H, W = x_shape
     Co, _, KH, KW = w_shape
-    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    (sh, sw), (ph, pw), (dh, dw) = ntuple(stride, 2), ntuple(padding, 2), ntuple(dilation, 2)
     arr = (ctypes.c_int * 14)(B, Ci, Co, H, W, KH, KW, sh, sw, ph, pw, dh, dw, groups)
     Ho = (H + 2 * ph - dh * (KH - 1) - 1) // sh + 1
     Wo = (W + 2 * pw - dw * (KW - 1) - 1) // sw + 1
@@ -36,11 +40,7 @@ def _geom(x_shape, w_shape, stride, padding, dilation, groups):
 
 
 def _scratch(device, nbytes):
-    key = _lib.scratch_key(device)
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = _ws_cache[key] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
-    return buf
+    return _lib.scratch("conv", device, nbytes, 1 << 16)
 
 
 _ktab_cache = {}
@@ -272,7 +272,7 @@ class ToChannelsLastFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, t):
-        ctx.planar = t.is_contiguous() and not t.is_contiguous(memory_format=torch.channels_last)
+        ctx.planar = is_planar(t)
         return to_channels_last(t)
 
     @staticmethod
@@ -803,7 +803,7 @@ class CplxConv2dFn(torch.autograd.Function):
         if ctx.x2:                       # float32 on IEEE-half pieces, channels-last in and out (see _x2_conv)
             from . import x3
             ctx.cl = False
-            ctx.x_planar = xr.is_contiguous() and not xr.is_contiguous(memory_format=torch.channels_last)
+            ctx.x_planar = is_planar(xr)
             xr, xi = (t.contiguous(memory_format=torch.channels_last) for t in (xr, xi))
             xp = x3.split_planes((_rows(xr), _rows(xi)), kind="x2")
             wr_, wi_ = wr.contiguous(), wi.contiguous()
@@ -816,7 +816,7 @@ class CplxConv2dFn(torch.autograd.Function):
         ctx.cl = xr.dtype == torch.bfloat16 and xi.dtype == torch.bfloat16 and _cl_ok(geom) and (
             _cl_wgrad_ok(geom) or not (wr.requires_grad or wi.requires_grad))
         if ctx.cl:                       # channels-last in, channels-last out: no layout copies between such layers
-            ctx.x_planar = xr.is_contiguous() and not xr.is_contiguous(memory_format=torch.channels_last)
+            ctx.x_planar = is_planar(xr)
             xr, xi = to_channels_last(xr), to_channels_last(xi)
             wcr, wci = ops.cast(wr.contiguous(), xr.dtype), ops.cast(wi.contiguous(), xr.dtype)
             yr, yi = cl_conv(xr, xi, wcr, wci, b[0], b[1], geom, moments=moments)
@@ -881,7 +881,7 @@ class RealConv2dFn(torch.autograd.Function):
         geom, oshape = _geom(x.shape, w.shape, stride, padding, dilation, groups)
         ctx.cl = _cl_layer_ok(geom, x)
         if ctx.cl:
-            ctx.x_planar = x.is_contiguous() and not x.is_contiguous(memory_format=torch.channels_last)
+            ctx.x_planar = is_planar(x)
             x = to_channels_last(x)
             wc = ops.cast(w.contiguous(), x.dtype)
             y = cl_conv_real(x, wc, None if b is None else b.contiguous(), geom)
@@ -936,7 +936,7 @@ def _circular_pad(t, padding):
     """symmetric_circular_padding (cplxmodule/cplx.py:701-714): ((p+1)//2, p//2) per spatial
     dim; F.pad's tuple starts at the LAST dim, the reference feeds `padding` in that order."""
     pads = []
-    for p in _pair(padding):
+    for p in ntuple(padding, 2):
         pads.extend(((p + 1) // 2, p // 2))
     return F.pad(t, tuple(pads), mode="circular")
 
@@ -972,7 +972,7 @@ def _pointwise_cl(xr, xi, w, stride, padding, groups):
     one conversion."""
     if not _CL_ENABLED or xr.dim() != 4 or xr.dtype != torch.bfloat16 or xi.dtype != torch.bfloat16 or not xr.is_cuda:
         return False
-    if tuple(w.shape[2:]) != (1, 1) or _pair(stride) != (1, 1) or _pair(padding) != (0, 0) or groups != 1:
+    if tuple(w.shape[2:]) != (1, 1) or ntuple(stride, 2) != (1, 1) or ntuple(padding, 2) != (0, 0) or groups != 1:
         return False
     B, C, H, W = xr.shape
     if B * H * W == 0 or C % 8 or w.shape[0] % 8:
@@ -991,7 +991,7 @@ class CplxConv2dLRTFn(torch.autograd.Function):
         geom, oshape = _geom(xr.shape, wr.shape, stride, padding, dilation, groups)
         ctx.cl = _cl_layer_ok(geom, xr, xi)
         if ctx.cl:      # channels-last end to end: mean conv, variance conv, noise injection all on [B][H][W][C] planes
-            ctx.x_planar = xr.is_contiguous() and not xr.is_contiguous(memory_format=torch.channels_last)
+            ctx.x_planar = is_planar(xr)
             xr, xi = to_channels_last(xr), to_channels_last(xi)
         else:
             xr, xi = xr.contiguous(), xi.contiguous()
@@ -1083,7 +1083,7 @@ class RealConv2dLRTFn(torch.autograd.Function):
         geom, oshape = _geom(x.shape, w.shape, stride, padding, dilation, groups)
         ctx.cl = _cl_layer_ok(geom, x)
         if ctx.cl:
-            ctx.x_planar = x.is_contiguous() and not x.is_contiguous(memory_format=torch.channels_last)
+            ctx.x_planar = is_planar(x)
             x = to_channels_last(x)
         else:
             x = x.contiguous()
@@ -1231,7 +1231,7 @@ def real_conv1d_layer(layer, input, eps=None):
 def _transpose_out_shape(x_shape, w_shape, stride, padding, output_padding, dilation, groups):
     B, Cin, H, W = x_shape
     _, Cog, KH, KW = w_shape
-    (sh, sw), (ph, pw), (oh, ow), (dh, dw) = (_pair(v) for v in (stride, padding, output_padding, dilation))
+    (sh, sw), (ph, pw), (oh, ow), (dh, dw) = (ntuple(v, 2) for v in (stride, padding, output_padding, dilation))
     return (B, Cog * groups, (H - 1) * sh - 2 * ph + dh * (KH - 1) + oh + 1,
             (W - 1) * sw - 2 * pw + dw * (KW - 1) + ow + 1)
 

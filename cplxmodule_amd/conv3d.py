@@ -23,13 +23,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, ops
-from ._lib import CplxAmdError, call, try_call, dtype_code, ptr, require_device, stream_ptr  # noqa: F401
+from ._lib import CplxAmdError, call, try_call, dtype_code, ntuple, ptr, require_device, stream_ptr  # noqa: F401
 from .cplx import Cplx
 from .conv import CplxConv2dFn, RealConv2dFn, _scratch
-
-
-def _triple(v):
-    return (v, v, v) if isinstance(v, int) else tuple(v)
 
 
 def _depth_out(D, k, s, p, d):
@@ -69,7 +65,7 @@ def _prepare(planes, kd, stride, padding, dilation, padding_mode):
 
 def cplx_conv3d(input, weight, bias=None, stride=1, padding=0, dilation=1, groups=1,
                 padding_mode="zeros"):
-    stride, padding, dilation = _triple(stride), _triple(padding), _triple(dilation)
+    stride, padding, dilation = ntuple(stride, 3), ntuple(padding, 3), ntuple(dilation, 3)
     kd = weight.shape[2]
     (xr, xi), pad2, Dout = _prepare([input.real, input.imag], kd, stride, padding, dilation, padding_mode)
     B = xr.shape[0]
@@ -86,7 +82,7 @@ def cplx_conv3d(input, weight, bias=None, stride=1, padding=0, dilation=1, group
 
 
 def real_conv3d(x, w, b=None, stride=1, padding=0, dilation=1, groups=1):
-    stride, padding, dilation = _triple(stride), _triple(padding), _triple(dilation)
+    stride, padding, dilation = ntuple(stride, 3), ntuple(padding, 3), ntuple(dilation, 3)
     kd = w.shape[2]
     (x,), pad2, Dout = _prepare([x], kd, stride, padding, dilation, "zeros")
     B = x.shape[0]
@@ -140,7 +136,7 @@ def _geom3(x_shape, w_shape, stride, padding, dilation, groups):
     output shape (asked of the library: one formula)."""
     B, Ci, D, H, W = x_shape
     Co, _, KD, KH, KW = w_shape
-    arr = (ctypes.c_int * 19)(B, Ci, Co, D, H, W, KD, KH, KW, *_triple(stride), *_triple(padding), *_triple(dilation),
+    arr = (ctypes.c_int * 19)(B, Ci, Co, D, H, W, KD, KH, KW, *ntuple(stride, 3), *ntuple(padding, 3), *ntuple(dilation, 3),
                               groups)
     out = (ctypes.c_int * 3)()
     if not try_call("cplxamd_conv3d_out_shape", arr, ctypes.byref(out, 0), ctypes.byref(out, 4), ctypes.byref(out, 8)):
@@ -153,7 +149,7 @@ def _geom3(x_shape, w_shape, stride, padding, dilation, groups):
 def _transpose_out_shape3(x_shape, w_shape, stride, padding, output_padding, dilation, groups):
     B, _, D, H, W = x_shape
     _, Cog, KD, KH, KW = w_shape
-    s, p, o, d = (_triple(v) for v in (stride, padding, output_padding, dilation))
+    s, p, o, d = (ntuple(v, 3) for v in (stride, padding, output_padding, dilation))
     ext = [(L - 1) * s[n] - 2 * p[n] + d[n] * (k - 1) + o[n] + 1 for n, (L, k) in enumerate(((D, KD), (H, KH), (W, KW)))]
     return (B, Cog * groups, *ext)
 
@@ -241,7 +237,7 @@ def _circular_pads(padding):
     """cplx.symmetric_circular_padding's F.pad argument: ((p + 1) // 2, p // 2) per entry of `padding`, and F.pad starts
     at the LAST dim -- padding[0] wraps W, padding[2] wraps D (cplxmodule/cplx.py:701-714)."""
     pads = []
-    for p in _triple(padding):
+    for p in ntuple(padding, 3):
         pads.extend(((p + 1) // 2, p // 2))
     return tuple(pads)
 
@@ -271,7 +267,7 @@ def cplx_conv_transpose3d(input, weight, bias=None, stride=1, padding=0, output_
     if input.dim() != 5 or weight.dim() != 5:
         raise ValueError(f"conv_transpose3d takes a [B, C, D, H, W] input and a [in, out / groups, kd, kh, kw] weight, got "
                          f"{tuple(input.shape)} and {tuple(weight.shape)}")
-    stride, output_padding, dilation = _triple(stride), _triple(output_padding), _triple(dilation)
+    stride, output_padding, dilation = ntuple(stride, 3), ntuple(output_padding, 3), ntuple(dilation, 3)
     circular = None
     if any(o < 0 or (o >= s and o >= d) for o, s, d in zip(output_padding, stride, dilation)):
         raise ValueError("output_padding must be smaller than either stride or dilation")
@@ -283,7 +279,7 @@ def cplx_conv_transpose3d(input, weight, bias=None, stride=1, padding=0, output_
         raise ValueError("padding_mode must be 'zeros' or 'circular'.")
     br, bi = (None, None) if bias is None else (bias.real, bias.imag)
     yr, yi = CplxConvTranspose3dFn.apply(input.real, input.imag, weight.real, weight.imag, br, bi, stride,
-                                         _triple(padding), output_padding, dilation, groups, circular)
+                                         ntuple(padding, 3), output_padding, dilation, groups, circular)
     return Cplx(yr, yi)
 
 
@@ -291,9 +287,9 @@ def cplx_max_pool3d(input, kernel_size, stride=None, padding=0, dilation=1, ceil
     """[B, C, D, H, W]: largest modulus over (h, w) per depth slice, then over the depth window --
     the same element (first maximum in (d, h, w) order) a direct 3-d scan selects."""
     from . import cplx
-    k = _triple(kernel_size)
-    s = k if stride is None else _triple(stride)
-    p, d = _triple(padding), _triple(dilation)
+    k = ntuple(kernel_size, 3)
+    s = k if stride is None else ntuple(stride, 3)
+    p, d = ntuple(padding, 3), ntuple(dilation, 3)
     B, C, D, H, W = input.shape
     flat = Cplx(input.real.reshape(B, C * D, H, W), input.imag.reshape(B, C * D, H, W))
     y = cplx.max_pool2d(flat, k[1:], s[1:], p[1:], d[1:], ceil_mode)

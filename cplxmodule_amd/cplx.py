@@ -12,7 +12,7 @@ from copy import deepcopy
 import torch
 
 from . import ops
-from ._lib import CplxAmdError
+from ._lib import CplxAmdError, ntuple
 
 
 class Cplx:
@@ -982,17 +982,13 @@ def dropout(input, p=0.5, training=True):
     return Cplx(*ops.CplxDropoutFn.apply(input.real, input.imag, p, seed, offset))
 
 
-def _pair2(v):
-    return (v, v) if isinstance(v, int) else tuple(v)
-
-
 def max_pool2d(input, kernel_size, stride=None, padding=0, dilation=1, ceil_mode=False):
     """Complex max pooling on [B, C, H, W]: the element of largest modulus in each window keeps
     both its parts (cplxmodule/cplx.py:1114-1175, 1183-1190)."""
-    k = _pair2(kernel_size)
-    s = k if stride is None else _pair2(stride)
-    return Cplx(*ops.CplxMaxPool2dFn.apply(input.real, input.imag, k, s, _pair2(padding),
-                                           _pair2(dilation), bool(ceil_mode)))
+    k = ntuple(kernel_size, 2)
+    s = k if stride is None else ntuple(stride, 2)
+    return Cplx(*ops.CplxMaxPool2dFn.apply(input.real, input.imag, k, s, ntuple(padding, 2),
+                                           ntuple(dilation, 2), bool(ceil_mode)))
 
 
 def max_pool1d(input, kernel_size, stride=None, padding=0, dilation=1, ceil_mode=False):

@@ -18,7 +18,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import CplxAmdError, call, ptr, require_device, stream_ptr
+from ._lib import CplxAmdError, call, ntuple, ptr, require_device, stream_ptr
 
 F64 = torch.float64
 
@@ -248,14 +248,10 @@ def real_linear_lrt(x, w, b, ls2, eps, seed=0, offset=0, kl_kind=None):
 # ------------------------------------------------------------------------------------------ #
 #  convolution                                                                               #
 # ------------------------------------------------------------------------------------------ #
-def _pair(v):
-    return (v, v) if isinstance(v, int) else tuple(v)
-
-
 def _geom(x_shape, w_shape, stride, padding, dilation, groups):
     B, Ci, H, W = x_shape
     Co, _, KH, KW = w_shape
-    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    (sh, sw), (ph, pw), (dh, dw) = ntuple(stride, 2), ntuple(padding, 2), ntuple(dilation, 2)
     Ho = (H + 2 * ph - dh * (KH - 1) - 1) // sh + 1
     Wo = (W + 2 * pw - dw * (KW - 1) - 1) // sw + 1
     if Ho <= 0 or Wo <= 0:

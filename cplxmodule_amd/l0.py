@@ -10,15 +10,12 @@ GEMM's operand loads is not done here.
 import torch
 
 from . import _lib, x3
-from ._lib import CplxAmdError, call, dtype_code, ptr, require_device, stream_ptr
+from ._lib import CplxAmdError, call, dtype_code, ptr, require_device, scratch, stream_ptr
+from ._lib import al16 as _al16
 from .ops import (_Pieces, _announce, _c, _f32, _noise_args, _real_linear_dw, _real_linear_dx, _real_linear_fwd, _ws,
                   colsum, grad_buffer, once_differentiable)
 
 COLS, TRAIN, HARD = 1, 2, 4          # include/cplxamd.h CPLXAMD_L0_*
-
-
-def _al16(t):
-    return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
 
 
 def _operand(t):
@@ -67,9 +64,6 @@ def gate_fwd(a, la, rows, cols, mode, u=None, seed=0, offset=0, bias=None, out_d
     return (out, tot) if total else out
 
 
-_bwd_ws = {}
-
-
 def gate_bwd(d, a, la, rows, cols, mode, u=None, seed=0, offset=0, da_dtype=None, az_dtype=None, da=None,
              dla=None):
     """(D (.) z [in `da` or a new da_dtype tensor; da_dtype False: not formed], A (.) z [az_dtype None: not formed],
@@ -88,11 +82,7 @@ def gate_bwd(d, a, la, rows, cols, mode, u=None, seed=0, offset=0, da_dtype=None
         dla = torch.empty(la.shape, dtype=torch.float32, device=d.device)
     ws, nb = None, 0
     if mode & COLS:
-        nb = int(_lib.load().cplxamd_l0_gate_bwd_ws_bytes(rows, cols))
-        key = _lib.scratch_key(d.device)
-        ws = _bwd_ws.get(key)
-        if ws is None or ws.numel() < nb:
-            ws = _bwd_ws[key] = torch.empty(max(nb, 1 << 16), dtype=torch.uint8, device=d.device)
+        ws = scratch("l0_bwd", d.device, int(_lib.load().cplxamd_l0_gate_bwd_ws_bytes(rows, cols)), 1 << 16)
         nb = ws.numel()
     pu, sd, of, st = _noise(u, seed, offset)
     call("cplxamd_l0_gate_bwd", ptr(d), ptr(a), ptr(la), pu, sd, of, st, ptr(da), ptr(az), ptr(dla), rows, cols, mode,

@@ -12,9 +12,8 @@ import functools
 import torch
 
 from . import _lib, x3
-from ._lib import CplxAmdError, call, dtype_code, launch_flags, ptr, require_device, scratch_key, stream_ptr, try_call
-
-_ws_cache = {}
+from ._lib import CplxAmdError, call, dtype_code, launch_flags, ptr, require_device, scratch, stream_ptr, try_call
+from ._lib import al16 as _al16
 
 
 def once_differentiable(fn):
@@ -47,12 +46,13 @@ def once_differentiable(fn):
     return wrapper
 
 
+@functools.lru_cache(maxsize=None)
+def _kl_ws_bytes():
+    return int(_lib.load().cplxamd_vd_kl_ws_bytes())
+
+
 def _ws(device):
-    key = scratch_key(device)
-    if key not in _ws_cache:
-        nbytes = int(_lib.load().cplxamd_vd_kl_ws_bytes())
-        _ws_cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return _ws_cache[key]
+    return scratch("kl", device, _kl_ws_bytes())
 
 
 def _c(t):
@@ -71,11 +71,6 @@ def _layout_of(t):
 
 def _cf(t, fmt):
     return None if t is None else t.contiguous(memory_format=fmt)
-
-
-def _al16(t):
-    """The streaming kernels move 16 bytes per lane: re-home the rare view that is not aligned."""
-    return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
 
 
 def _f32(t):
@@ -117,24 +112,42 @@ def colsum(t, out=None):
         dst, out = out, torch.empty(C, dtype=torch.float32, device=t.device)
     else:
         dst = None
-    ws = torch.empty(int(_lib.load().cplxamd_colsum_ws_bytes(C)), dtype=torch.uint8, device=t.device)
+    ws = _colsum_ws(t.device, int(_lib.load().cplxamd_colsum_ws_bytes(C)))
     call("cplxamd_colsum", ptr(t), C, ptr(out), R, C, dtype_code(t), ptr(ws), stream_ptr())
     return out if dst is None else dst.copy_(out)
+
+
+# ---- hints: what a producer leaves on the tensors it returns, for the consumer that gets exactly those tensors --------
+# THE rule, stated once: a hint holds for the same tensor objects, the same storage, unmodified since (version counter),
+# the recorded shape, on every plane.  A stale hint would be a silently wrong gradient.  (The `_cplxamd_conv_src` tag of
+# conv.py / bn.py is not a hint: an unvalidated weak reference that only arms an epilogue for the NEXT step.)
+def leave(name, planes, payload):
+    """Record `payload` under `name` on planes[0], with (data_ptr, _version) of every plane and the shape."""
+    setattr(planes[0], "_cplxamd_" + name, (payload, planes[0].shape, [(t.data_ptr(), t._version) for t in planes]))
+
+
+def take(name, planes):
+    """The payload `leave` recorded for exactly these planes, or None."""
+    h = getattr(planes[0], "_cplxamd_" + name, None)
+    if h is None:
+        return None
+    for t, (address, version) in zip(planes, h[2]):      # (a plain loop: this runs several times per eager step)
+        if t.data_ptr() != address or t._version != version or t.shape != h[1]:
+            return None
+    return h[0]
 
 
 def attach_colsum(t, sums):
     """Remember on the tensor object that `sums` (float32 [C]) holds its per-channel sums over every other dimension:
     a producer that had all values in registers anyway (the batch-norm backward) leaves them for the consumer's bias
     gradient.  Validated on use against the storage address and the version counter."""
-    t._cplxamd_colsum = (sums, t.data_ptr(), t._version, tuple(t.shape))
+    leave("colsum", (t,), sums)
 
 
 def colsum_hint(t):
     """The sums attach_colsum left on exactly this tensor (same storage, unmodified since), or None."""
-    h = getattr(t, "_cplxamd_colsum", None)
-    if h is not None and h[1] == t.data_ptr() and h[2] == t._version and h[3] == tuple(t.shape) and h[0].numel() == t.shape[1]:
-        return h[0]
-    return None
+    sums = take("colsum", (t,))
+    return sums if sums is not None and sums.numel() == t.shape[1] else None
 
 
 def attach_scale(tr, ti, scale):
@@ -142,48 +155,37 @@ def attach_scale(tr, ti, scale):
     format) is the power-of-two scale of max |.| over both: the producer (the batch-norm backward's apply pass) had every
     value in registers; the consumer that cuts the planes into half pieces (x3 'x2') skips its absmax pass.  Validated on
     use like attach_colsum."""
-    tr._cplxamd_scale = (scale, tr.data_ptr(), tr._version, ti.data_ptr(), ti._version, tuple(tr.shape))
+    leave("scale", (tr, ti), scale)
 
 
 def scale_hint(tr, ti):
     """The scale attach_scale left for exactly this pair of planes (same storage, unmodified since), or None."""
-    h = getattr(tr, "_cplxamd_scale", None)
-    if (h is not None and h[1] == tr.data_ptr() and h[2] == tr._version and h[3] == ti.data_ptr() and h[4] == ti._version
-            and h[5] == tuple(tr.shape) == tuple(ti.shape)):
-        return h[0]
-    return None
+    return take("scale", (tr, ti))
 
 
 def attach_wgrad(tr, ti, dw):
     """Remember on the two planes of a convolution's output gradient that `dw` = (dW_r, dW_i) is the weight gradient of
     exactly these planes against the input of the convolution whose autograd node is `node` (bn.py: the batch-norm
     backward that formed the planes inside the weight-gradient kernel).  Validated on use like attach_colsum."""
-    tr._cplxamd_wgrad = (dw, tr.data_ptr(), tr._version, ti.data_ptr(), ti._version, tuple(tr.shape))
+    leave("wgrad", (tr, ti), dw)
 
 
 def wgrad_hint(tr, ti, node):
     """(dW_r, dW_i) attach_wgrad left for exactly this pair of planes and this convolution node, or None."""
-    h = getattr(tr, "_cplxamd_wgrad", None)
-    if (h is not None and h[1] == tr.data_ptr() and h[2] == tr._version and h[3] == ti.data_ptr() and h[4] == ti._version
-            and h[5] == tuple(tr.shape) == tuple(ti.shape) and h[0][2] is node):
-        return h[0][0], h[0][1]
-    return None
+    dw = take("wgrad", (tr, ti))
+    return (dw[0], dw[1]) if dw is not None and dw[2] is node else None
 
 
 def attach_moments(tr, ti, partials, chunks):
     """Remember on the two planes of a convolution output that `partials` ([chunks][C][5] float64) holds the batch-norm
     forward moments of exactly these tensors (conv.cl_conv, csrc/conv_cl2.hip MOM epilogue): the batch-norm layer that
     consumes them skips its own moment pass.  Validated on use like attach_colsum."""
-    tr._cplxamd_moments = (partials, int(chunks), tr.data_ptr(), tr._version, ti.data_ptr(), ti._version, tuple(tr.shape))
+    leave("moments", (tr, ti), (partials, int(chunks)))
 
 
 def moments_hint(tr, ti):
     """(partials, chunks) attach_moments left for exactly this pair of planes (same storage, unmodified since), or None."""
-    h = getattr(tr, "_cplxamd_moments", None)
-    if (h is not None and h[2] == tr.data_ptr() and h[3] == tr._version and h[4] == ti.data_ptr() and h[5] == ti._version
-            and h[6] == tuple(tr.shape) == tuple(ti.shape)):
-        return h[0], h[1]
-    return None
+    return take("moments", (tr, ti))
 
 
 def colsum2(tr, ti, out=None):
@@ -193,7 +195,7 @@ def colsum2(tr, ti, out=None):
         tr, ti = tr.contiguous(), ti.contiguous()
         R, C = tr.shape
         o = torch.empty(2, C, dtype=torch.float32, device=tr.device)
-        ws = torch.empty(int(_lib.load().cplxamd_colsum_ws_bytes(C)), dtype=torch.uint8, device=tr.device)
+        ws = _colsum_ws(tr.device, int(_lib.load().cplxamd_colsum_ws_bytes(C)))
         call("cplxamd_colsum2", ptr(tr), ptr(ti), C, ptr(o[0]), ptr(o[1]), R, C, dtype_code(tr), ptr(ws), stream_ptr())
         return o[0], o[1]
     return colsum(tr, None if out is None else out[0]), colsum(ti, None if out is None else out[1])
@@ -240,33 +242,16 @@ def exp(x, out_dtype=torch.float32):
     return out
 
 
-_gemm_ws_cache = {}
-
-
 def _gemm_ws(M, N, K, cplx, a, c):
     """Split-K scratch (asked for by few-tile / long-K GEMMs: wgrad at large batch, small heads)."""
     # (half pieces run the bf16 path's kernels compiled for the half MFMA: same split-K plan)
     need = int(_lib.load().cplxamd_gemm_ws_bytes(M, N, K, int(cplx), _lib.BF16 if a.dtype == torch.float16 else dtype_code(a),
                                                  dtype_code(c)))
-    if need == 0:
-        return None
-    key = scratch_key(a.device)
-    buf = _gemm_ws_cache.get(key)
-    if buf is None or buf.numel() < need:
-        buf = _gemm_ws_cache[key] = torch.empty(need, dtype=torch.uint8, device=a.device)
-    return buf
-
-
-_gauss_ws_cache = {}
+    return scratch("gemm", a.device, need) if need else None
 
 
 def _gauss_ws(M, N, K, device):
-    need = int(_lib.load().cplxamd_cgemm3m_ws_bytes(M, N, K))
-    key = scratch_key(device)
-    buf = _gauss_ws_cache.get(key)
-    if buf is None or buf.numel() < need:
-        buf = _gauss_ws_cache[key] = torch.empty(need, dtype=torch.uint8, device=device)
-    return buf
+    return scratch("gauss", device, int(_lib.load().cplxamd_cgemm3m_ws_bytes(M, N, K)))
 
 
 def gauss_ok(M, N, K):
@@ -434,14 +419,7 @@ def reparam_fwd(mu_r, mu_i, s2, eps=None, seed=0, offset=0, inplace=False):
 
 
 def _colsum_ws(device, nbytes):
-    key = scratch_key(device)
-    buf = _colsum_ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = _colsum_ws_cache[key] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-    return buf
-
-
-_colsum_ws_cache = {}
+    return scratch("colsum", device, nbytes, 1 << 20)
 
 
 def _as_rows(t, rows, cols):
@@ -485,7 +463,7 @@ def reparam_bwd(g_r, g_i, s2, eps=None, seed=0, offset=0, out_dtype=torch.float3
                  ptr(g_s2), g_r.numel(), dtype_code(g_r), dtype_code(g_s2), dtype_code(s2), stream_ptr())
             if g_i is not None:                  # both planes' bias sums in one launch
                 a_r, a_i = _as_rows(g_r, rows, cols).contiguous(), _as_rows(g_i, rows, cols).contiguous()
-                cws = torch.empty(int(_lib.load().cplxamd_colsum_ws_bytes(cols)), dtype=torch.uint8, device=g_r.device)
+                cws = _colsum_ws(g_r.device, int(_lib.load().cplxamd_colsum_ws_bytes(cols)))
                 call("cplxamd_colsum2", ptr(a_r), ptr(a_i), cols, ptr(sum_r), ptr(sum_i), rows, cols, dtype_code(a_r), ptr(cws),
                      stream_ptr())
             else:

@@ -9,6 +9,7 @@ from torch's caching allocator, and nothing here reads a device value on the hos
 hipGraph.
 """
 import ctypes
+import functools
 import math
 
 import torch
@@ -20,21 +21,12 @@ from .ops import once_differentiable
 MAX_N = 1 << 22                       # CPLXAMD_WELCH_MAX_N
 SCALING = {"density": 0, "spectrum": 1}
 PATHS = ("direct", "four-step", "bluestein", "bluestein+four-step")   # cplxamd_welch_plan's return codes
+_code = functools.partial(_lib.plane_code, "Welch spectra take float32, bfloat16 or float64 planes (complex64 / complex128)")
 
 
 def compute_dtype(dtype):
     """dtype of the spectrum of planes of `dtype`: bf16 planes are computed in, and give, float32"""
     return torch.float64 if dtype == torch.float64 else torch.float32
-
-
-def _code(dtype):
-    if dtype == torch.float32:
-        return _lib.F32
-    if dtype == torch.bfloat16:
-        return _lib.BF16
-    if dtype == torch.float64:
-        return _lib.F64
-    raise CplxAmdError(f"Welch spectra take float32, bfloat16 or float64 planes (complex64 / complex128), got {dtype}")
 
 
 def plan(n, rows, segments, dtype=torch.float32):

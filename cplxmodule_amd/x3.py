@@ -35,13 +35,14 @@ for half pieces; float32 output, accumulate from the second launch on):
                                       float32 output -- which is small ([O, I])
 Smallest terms first in every sequence.
 """
+import functools
 import os
 import threading
 
 import torch
 
 from . import _lib
-from ._lib import call, ptr, require_device, scratch_key, stream_ptr
+from ._lib import call, ptr, require_device, scratch, stream_ptr
 
 SPLIT_A, SPLIT_B = 0, 1
 OP_ID, OP_ABS2, OP_EXP, OP_MAX2 = 0, 1, 2, 3
@@ -130,14 +131,13 @@ class Pieces:
         self.t, self.kind, self.scale, self.n = t, kind, scale, n
 
 
-_abs_ws = {}
+@functools.lru_cache(maxsize=None)
+def _absmax_ws_bytes():
+    return int(_lib.load().cplxamd_absmax_ws_bytes())
 
 
 def _absmax_ws(device):
-    key = scratch_key(device)
-    if key not in _abs_ws:
-        _abs_ws[key] = torch.empty(int(_lib.load().cplxamd_absmax_ws_bytes()), dtype=torch.uint8, device=device)
-    return _abs_ws[key]
+    return scratch("absmax", device, _absmax_ws_bytes())
 
 
 def _dense(t, t2=None):

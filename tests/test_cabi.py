@@ -47,6 +47,53 @@ def test_python_binding_matches_header(lib):
     assert _lib.load().cplxamd_abi_version() == _lib.ABI_VERSION
 
 
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float,
+            "double": ctypes.c_double}
+
+
+def _ctype(decl, where):
+    """ctypes type of one C declarator (`const float* x`, `int geom[14]`, `int64_t n`, a bare return type); a type this
+    table does not know fails the test."""
+    decl = " ".join(decl.split())
+    if "*" in decl or decl.endswith("]"):
+        return ctypes.c_void_p
+    words = [w for w in decl.split(" ") if w != "const"]
+    assert 1 <= len(words) <= 2 and words[0] in _SCALARS, f"{where}: no ctypes mapping for `{decl}`"
+    return _SCALARS[words[0]]
+
+
+def prototypes():
+    """name -> (restype, [argtypes]) of every cplxamd_* prototype of the header."""
+    src = open(HEADER).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    src = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", "", src, flags=re.M)            # preprocessor lines
+    out = {}
+    for ret, name, args in re.findall(r"(\w[\w \t*]*?)\s*\b(cplxamd_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in out, f"{name} is declared twice"
+        params = [] if args.strip() in ("", "void") else args.split(",")
+        out[name] = (_ctype(ret, name), [_ctype(p, name) for p in params])
+    return out
+
+
+def test_python_binding_matches_header_types():
+    """_lib.SIGNATURES is a hand-kept copy of the header's prototypes: an `int` bound as int64_t, or a pointer bound as an
+    integer, corrupts the call on the GPU and nothing on the CPU notices.  Every argument and return type, one by one."""
+    from cplxmodule_amd import _lib
+    protos = prototypes()
+    # the reader dropped no declaration: as many prototypes as names followed by `(`, and as many as the table binds
+    assert sorted(protos) == declared_symbols()
+    assert len(protos) == len(_lib.SIGNATURES)
+    for name, (restype, argtypes) in protos.items():
+        bound = _lib.SIGNATURES[name]
+        assert len(bound) == len(argtypes), f"{name}: {len(bound)} arguments bound, {len(argtypes)} declared"
+        for i, (b, a) in enumerate(zip(bound, argtypes)):
+            assert b is a, f"{name}: argument {i} is bound as {b.__name__}, declared as {a.__name__}"
+        got = _lib._RESTYPES.get(name, ctypes.c_int)
+        assert got is restype, f"{name}: returns {restype.__name__}, bound as {got.__name__}"
+    assert set(_lib._RESTYPES) <= set(protos)
+
+
 def test_no_gpu_arguments_are_rejected_not_crashed(lib):
     """Argument validation happens before any launch: callable without a GPU."""
     lib.cplxamd_vd_kl_fwd.restype = ctypes.c_int

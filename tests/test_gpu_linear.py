@@ -427,3 +427,36 @@ def test_cgemm_f32_generic_split_k(pkg, M, N_, K, conj):
     c = ops.rgemm(T(ar), (K, 1), T(br), (K, 1), M, N_, K, emul=T(em))
     rref = (ar.astype(f) @ br.astype(f).T) * em
     np.testing.assert_allclose(N(c), rref, rtol=1e-5, atol=2e-6 * np.sqrt(K) * np.abs(rref).max() / 10)
+
+
+def test_scratch_workspaces_are_per_stream(pkg):
+    """_lib.scratch keys its buffers by stream: the column sums of a matrix taller than one workgroup's row chunk (the
+    workspace holds the partial sums) and a bf16 linear step run on two side streams give the default stream's bits,
+    each through a workspace of its own."""
+    from cplxmodule_amd import ops
+    dev = torch.device("cuda", torch.cuda.current_device())
+    torch.manual_seed(0)
+    m = torch.randn(3000, 40, device=dev)
+    x = [torch.randn(64, 96, device=dev).bfloat16() for _ in range(2)]
+    params = [torch.randn(80, 96, device=dev) for _ in range(2)] + [torch.randn(80, device=dev) for _ in range(2)]
+    g = tuple(torch.randn(64, 80, device=dev).bfloat16() for _ in range(2))
+
+    def run():
+        leaves = [t.clone().requires_grad_(True) for t in x + params]
+        y = ops.CplxLinearFn.apply(*leaves)
+        torch.autograd.backward(y, g)
+        return [ops.colsum(m), *y] + [t.grad for t in leaves], ops._colsum_ws(dev, 1).data_ptr()
+
+    want, ptr0 = run()
+    torch.cuda.synchronize()
+    ptrs = {ptr0}
+    for _ in range(2):
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            got, p = run()
+        side.synchronize()
+        assert len(got) == len(want) == 9
+        for a, b in zip(got, want):
+            assert torch.equal(a, b)
+        ptrs.add(p)
+    assert len(ptrs) == 3
