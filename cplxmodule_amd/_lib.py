@@ -235,6 +235,9 @@ SIGNATURES = {
     "cplxamd_filtfilt_plan": [_L, _L, _L, _L, _L, _L, _I, _I, _L, _P],
     "cplxamd_filtfilt_src": [_L, _L, _L, _I, _P],
     "cplxamd_filtfilt_pass": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    # still ABI 25: the chirp-z transform behind cplx.czt / zoom_fft (csrc/czt.hip; the descriptor is CztDesc)
+    "cplxamd_czt_plan": [_L, _L, _L, _I, _P, _P],
+    "cplxamd_czt": [_P, _P, _P, _P, _P, _I, _I, _P, _L, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -247,13 +250,24 @@ class EinsumDesc(ctypes.Structure):
                 ("stride_b", (c_int64 * 8) * 4), ("stride_c", (c_int64 * 8) * 4)]
 
 
-# The descriptors of the signal kernels (Fft, FftConv, Upfirdn, Iir, FiltFilt) carry up to three batch runs: _runs.py fuses
+# The descriptors of the signal kernels (Fft, Czt, FftConv, Upfirdn, Iir, FiltFilt) carry up to three batch runs: _runs.py fuses
 # the dims into runs and writes them here (`fill`), csrc/runs.h decodes them (`decode_runs`).
 class FftDesc(ctypes.Structure):
     """cplxamd_fft_desc: one transformed dim (n, n_in, element strides) and up to three batch runs, run 0 outermost."""
     _fields_ = [("n", c_int64), ("n_in", c_int64), ("x_es", c_int64), ("y_es", c_int64), ("runs", ctypes.c_int32),
                 ("inverse", ctypes.c_int32), ("size", c_int64 * 3), ("x_stride", c_int64 * 3), ("y_stride", c_int64 * 3),
                 ("scale", c_double)]
+
+
+class CztDesc(ctypes.Structure):
+    """cplxamd_czt_desc: inputs and outputs per vector (n, m), element strides, up to three batch runs (run 0 outermost),
+    the contour (log-modulus and turn fraction of w and of a) and the scale."""
+    _fields_ = [("n", c_int64), ("m", c_int64), ("x_es", c_int64), ("y_es", c_int64), ("runs", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("size", c_int64 * 3), ("x_stride", c_int64 * 3), ("y_stride", c_int64 * 3),
+                ("w_log", c_double), ("w_turn", c_double), ("a_log", c_double), ("a_turn", c_double), ("scale", c_double)]
+
+
+CZT_A_OUT = 1                                             # CPLXAMD_CZT_A_OUT
 
 
 class StftDesc(ctypes.Structure):

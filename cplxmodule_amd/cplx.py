@@ -836,6 +836,41 @@ def fftconvolve(input, other, mode="full"):
     return _fftconv.fftconvolve(input, other, mode)
 
 
+# ---- chirp-z transforms (arguments and results as scipy.signal's): m bins on any arc or spiral of the z-plane from n
+# samples, on one fused kernel (cplxmodule_amd/czt.py, csrc/czt.hip) ---------------------------------------------------------
+def czt(x, m=None, w=None, a=1 + 0j):
+    r"""Chirp-z transform y_k = sum_j x_j a^{-j} w^{jk}, k = 0 .. m - 1, along the last dim, as `scipy.signal.czt`: the
+    z-transform of every vector at the points a w^{-k}.  `m` defaults to the number of samples n, `w` to e^{-2 pi i / m};
+    `w` and `a` are Python numbers (no tensors, no gradient).  `x` is a `Cplx` or a real tensor (a null imaginary plane:
+    no zero plane is built) of float32, bfloat16 (float32 arithmetic, one rounding) or float64 on the device; leading dims
+    are batch and are read in place.  The result is a `Cplx` [..., m] in the input's dtype and memory order.  Up to
+    n + m - 1 <= 8192 one launch reads n and writes m entries per vector; up to 2^22 the transform goes through a
+    workspace.  `czt(x)` of a `Cplx` with the default `w`, a == 1 and a power of two m >= n is a zero-padded FFT and calls
+    `cplx.fft`'s kernel (any other m is no shorter a convolution there than here).  Deterministic, capturable in a hipGraph, differentiable to any order in `x`.
+
+    Off the unit circle the algorithm's tables span a factor e^D, D = |ln|w|| max(n, m)^2 / 2 + |ln|a|| n, and the error
+    follows eps e^D (scipy's does too, silently); a contour with D > ln 2^24 (float32, bfloat16) or ln 2^53 (float64)
+    leaves no correct digit and raises CplxAmdError."""
+    from . import czt as _czt
+    return _czt.czt(x, m, w, a)
+
+
+def zoom_fft(x, fn, m=None, fs=2, endpoint=False):
+    r"""The DFT of the last dim on `m` (default n) equally spaced frequencies of the band `fn` = (f1, f2) (a scalar: (0,
+    fn)) at sampling rate `fs`, as `scipy.signal.zoom_fft`: `czt` with w = e^{-2 pi i scale / m}, a = e^{2 pi i f1 / fs},
+    scale = (f2 - f1) / fs (with `endpoint`: times m / (m - 1), so that f2 is the last bin).  The kernel receives the
+    fractions -scale / m and f1 / fs themselves, not a complex number to take the argument of."""
+    from . import czt as _czt
+    return _czt.zoom_fft(x, fn, m, fs, endpoint)
+
+
+def czt_points(m, w=None, a=1 + 0j):
+    r"""The points a w^{-k}, k = 0 .. m - 1, at which `czt` evaluates the z-transform, as `scipy.signal.czt_points`: a
+    complex128 tensor on the host."""
+    from . import czt as _czt
+    return _czt.czt_points(m, w, a)
+
+
 def upfirdn(h, x, up=1, down=1):
     r"""Upsample by `up`, FIR filter, downsample by `down` along the last dim, with the argument order and the result of
     `scipy.signal.upfirdn` (`mode="constant"`): y[n] = sum_k h[k] xu[n down - k] where xu[i up] = x[i] and zero

@@ -1525,6 +1525,46 @@ int cplxamd_expand_weight(const void* src_r, const void* src_i, const float* mas
                           void* out_r, void* out_i, int64_t O, int64_t C, int64_t T, int64_t n_rows, int64_t n_cols,
                           int in_dtype, int out_dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Chirp-z transforms of planar complex tensors (cplx.czt / zoom_fft; csrc/czt.hip on the engine of csrc/fft_engine.h).
+ * New exports under ABI 25: nothing existing changes.  With w = e^{w_log + 2 pi i w_turn}, a = e^{a_log + 2 pi i a_turn}:
+ *   y[v][k] = scale * sum_{j < n} x[v][j] a^{-j} w^{jk},  k in [0, m)                       (flags = 0)
+ *   y[v][k] = scale * a^{-k} sum_{j < n} x[v][j] w^{jk},  k in [0, m)                       (CPLXAMD_CZT_A_OUT)
+ * for every vector v of the batch; the adjoint of the first form with (n, m, w, a) is the second with (m, n, conj w, conj
+ * a), i.e. both turn fractions negated.  Planes, element strides and batch runs are cplxamd_fft's (x strides may be zero,
+ * x and y must not overlap); x_i may be NULL: a plane of zeros that is never read.  Dtype pairs (in, out) as cplxamd_fft:
+ * bf16 is widened on load, the arithmetic is float32 (float64 for F64), every output is rounded once, on store.
+ * The transform is Bluestein's convolution of length n + m - 1 at M = 2^ceil(log2(n + m - 1)), M >= 8.  cplxamd_czt_plan is
+ * a pure function (no GPU): it returns the path (CPLXAMD_CZT_*), how many vectors one workgroup transforms (2048 / M when
+ * packed, else 1) and the workspace bytes (nullable outputs); CPLXAMD_EINVAL for n or m < 1, negative `vectors` or a bad
+ * dtype, CPLXAMD_ESHAPE for M above CPLXAMD_WELCH_MAX_N.  cplxamd_czt goes through the same plan and checks every argument
+ * before any launch: CPLXAMD_EINVAL (NULL pointer other than x_i -- the workspace included --, bad dtype pair, n / m /
+ * strides / runs / sizes out of range, unknown flags, a contour parameter or scale that is not finite), CPLXAMD_ESHAPE (M
+ * too large, more than 2^31 - 1 vectors), CPLXAMD_EWS (workspace smaller than the plan's).  Zero vectors: no launch,
+ * returns 0.  The tables of a call (twiddles, opening and closing chirp, B-hat) are built in its workspace, in float64
+ * from the log-moduli and turn fractions (the phase theta i^2 / 2 mod 1 exactly reduced) and rounded once: no state in the
+ * library, no atomics, the same input gives the same bits, capturable in a hipGraph.  Off the unit circle the tables span
+ * a factor e^D, D = |w_log| max(n, m)^2 / 2 + |a_log| n, and the result loses that much precision (a property of the
+ * algorithm): callers should refuse D beyond ln 2^24 (float32) / ln 2^53 (float64); the library does not look at D.
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_CZT_PACKED = 0,               /* M <= 1024: 2048 / M vectors per 256-thread workgroup, one launch        */
+       CPLXAMD_CZT_FUSED = 1,                /* M = 2048 .. 8192: one vector per workgroup, one launch                  */
+       CPLXAMD_CZT_WORKSPACE = 2             /* M above that: through the workspace (four-step above the LDS limit)     */ };
+enum { CPLXAMD_CZT_A_OUT = 1                 /* the power of a multiplies the outputs (a^{-k}), not the inputs          */ };
+typedef struct cplxamd_czt_desc {
+  int64_t n, m;         /* inputs read and outputs written per vector, each >= 1, n + m - 1 <= 2^22 */
+  int64_t x_es, y_es;   /* element strides along the transformed dim, in elements; x_es >= 0, y_es >= 1 */
+  int32_t runs;         /* 0 .. 3 batch runs, run 0 outermost */
+  int32_t flags;        /* CPLXAMD_CZT_* bits */
+  int64_t size[3], x_stride[3], y_stride[3];
+  double  w_log, w_turn;  /* ln |w| and arg(w) / 2 pi */
+  double  a_log, a_turn;  /* ln |a| and arg(a) / 2 pi */
+  double  scale;        /* multiplies the result in the epilogue, before its one rounding */
+} cplxamd_czt_desc;     /* 152 bytes */
+int cplxamd_czt_plan(int64_t n, int64_t m, int64_t vectors, int dtype, int* vectors_per_workgroup, int64_t* ws_bytes);
+int cplxamd_czt(const void* x_r, const void* x_i, void* y_r, void* y_i, const cplxamd_czt_desc* d,
+                int in_dtype, int out_dtype, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
