@@ -238,6 +238,11 @@ SIGNATURES = {
     # still ABI 25: the chirp-z transform behind cplx.czt / zoom_fft (csrc/czt.hip; the descriptor is CztDesc)
     "cplxamd_czt_plan": [_L, _L, _L, _I, _P, _P],
     "cplxamd_czt": [_P, _P, _P, _P, _P, _I, _I, _P, _L, _P],
+    # still ABI 25: scaled dot-product attention behind cplx.scaled_dot_product_attention (csrc/attention.hip; the
+    # descriptor is AttnDesc, the plan fills ATTN_PLAN_FIELDS int64)
+    "cplxamd_attn_plan": [_L, _L, _L, _L, _L, _I, _P],
+    "cplxamd_attn_fwd": [_P] * 10 + [_I, _P],
+    "cplxamd_attn_bwd": [_P] * 18 + [_I, _P, _L, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -268,6 +273,21 @@ class CztDesc(ctypes.Structure):
 
 
 CZT_A_OUT = 1                                             # CPLXAMD_CZT_A_OUT
+
+
+class AttnDesc(ctypes.Structure):
+    """cplxamd_attn_desc: queries, keys and head sizes (L, S, E, Ev), up to three batch runs (run 0 outermost) with the
+    strides of q, k, v, o, the log-sum-exp and (backward) dq, dk, dv, the row strides, flags and the scale."""
+    _fields_ = [("L", c_int64), ("S", c_int64), ("E", c_int64), ("Ev", c_int64), ("runs", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("size", c_int64 * 3), ("q_stride", c_int64 * 3), ("k_stride", c_int64 * 3),
+                ("v_stride", c_int64 * 3), ("o_stride", c_int64 * 3), ("lse_stride", c_int64 * 3), ("dq_stride", c_int64 * 3),
+                ("dk_stride", c_int64 * 3), ("dv_stride", c_int64 * 3), ("q_rs", c_int64), ("k_rs", c_int64), ("v_rs", c_int64),
+                ("o_rs", c_int64), ("dq_rs", c_int64), ("dk_rs", c_int64), ("dv_rs", c_int64), ("scale", c_double)]
+
+
+# fields of cplxamd_attn_plan's output (CPLXAMD_ATTN_*) and the flag bits
+ATTN_PLAN_FIELDS = ("q_tile", "k_tile", "head", "q_tiles", "grid", "lds_bytes", "ws_bytes")
+ATTN_CAUSAL, ATTN_ABS = 1, 2
 
 
 class StftDesc(ctypes.Structure):

@@ -1045,3 +1045,18 @@ def max_pool3d(input, kernel_size, stride=None, padding=0, dilation=1, ceil_mode
 # float64: a parity mode on its own kernels (f64.py)
 _BatchedMatmulFn = ops.Route(_BatchedMatmulFn, "matmul_batched")
 _MatmulFn = ops.Route(_MatmulFn, "matmul2d")
+
+
+# ---- attention: softmax(scale Re(q k^H)) v or softmax(scale |q k^H|) v on one fused flash kernel
+# (cplxmodule_amd/attention.py, csrc/attention.hip) -------------------------------------------------------------------
+def scaled_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.0, is_causal=False, scale=None,
+                                 score="real"):
+    r"""Scaled dot-product attention of `Cplx` tensors query [..., L, E], key [..., S, E], value [..., S, Ev] -> [..., L, Ev];
+    names and order as `torch.nn.functional.scaled_dot_product_attention`, `score` appended.  With c = q k^H, the scores are
+    scale Re c (`score="real"`) or scale |c| (`"abs"`), p = softmax over the keys is real and o = p v complex.  `scale`
+    defaults to 1 / sqrt(E) (the real variant equals torch attention on concatenated planes when that scale is passed
+    there).  `is_causal` masks j > i, top-left aligned.  float32 and bfloat16 run one fused launch that keeps the scores
+    in registers; float64 takes the composed route.  `attn_mask`, dropout, E or Ev above 128, broadcast or
+    grouped heads raise `CplxAmdError`.  Differentiable once; the leading dims are read in place through strides."""
+    from . import attention as _attention
+    return _attention.scaled_dot_product_attention(query, key, value, attn_mask, dropout_p, is_causal, scale, score)

@@ -18,7 +18,11 @@ for f in *.hip; do
     if [ ! -f "$o" ] || [ "$h" -nt "$o" ]; then stale=1; fi
   done
   if [ $stale = 1 ]; then
-    $HIPCC $FLAGS -c "$f" -o "$o" &
+    # (a source may ask for flags of its own on a first line `// hipcc-flags: ...`; the line is part of the source, so
+    # changing it makes the object stale like any other edit.  attention.hip turns packed float32 operations off:
+    # DESIGN 25.3)
+    extra=$(sed -n '1s|^// hipcc-flags: ||p' "$f")
+    $HIPCC $FLAGS $extra -c "$f" -o "$o" &
     pids+=($!)
   fi
 done

@@ -1565,6 +1565,53 @@ int cplxamd_czt_plan(int64_t n, int64_t m, int64_t vectors, int dtype, int* vect
 int cplxamd_czt(const void* x_r, const void* x_i, void* y_r, void* y_i, const cplxamd_czt_desc* d,
                 int in_dtype, int out_dtype, void* ws, int64_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Scaled dot-product attention of planar complex tensors (cplx.scaled_dot_product_attention; csrc/attention.hip).
+ * New exports under ABI 25: nothing existing changes.  Per batch entry, with c = q k^H (Hermitian product):
+ *   s = scale Re c  (flags = 0)   or   s = scale |c|  (CPLXAMD_ATTN_ABS),   masked to j <= i under CPLXAMD_ATTN_CAUSAL,
+ *   p = softmax_j s  (real),   o = p v  (complex),   lse_i = log sum_j exp s_ij  (float32).
+ * q is [L, E], k [S, E], v [S, Ev], o [L, Ev] per batch entry; the last dim of every tensor has stride 1, rows lie
+ * *_rs elements apart and batch entries are found through up to three runs (run 0 outermost), strides in elements; lse,
+ * and the backward's workspace, hold one float per (batch, query): lse through its own run strides with row stride 1.
+ * Planes of one tensor share its strides.  dtype is CPLXAMD_F32 (the exact float32 matrix instruction) or CPLXAMD_BF16
+ * (bf16 matrix instruction, float32 accumulation and statistics, p rounded to bf16 once, o rounded once) and holds for
+ * q, k, v, o, the gradients included.  cplxamd_attn_plan is a pure function (no GPU) and fills
+ * plan[CPLXAMD_ATTN_PLAN_FIELDS]; cplxamd_attn_fwd is ONE launch that writes o and lse; cplxamd_attn_bwd takes the
+ * upstream gradient g in o's layout and writes dq, dk, dv through the dq / dk / dv strides of the descriptor (a small
+ * pass forms D_i = Re(g^H o)_i in the workspace, one kernel per query tile writes dq, one per key tile dk and dv: p is
+ * recomputed from lse, nothing of size L x S is in memory, no atomics).  dq_r and dq_i may both be NULL, and so may
+ * dk_r, dk_i, dv_r and dv_i together: the kernel that would write them is not launched.  Every argument is checked before any launch:
+ * CPLXAMD_EINVAL (NULL pointer, bad dtype, sizes < 1, E or Ev > 128, negative strides, unknown flags, a scale that is not
+ * finite), CPLXAMD_ESHAPE (L, S or the grid beyond 2^31 - 1), CPLXAMD_EWS.  An empty batch: no launch, returns 0.
+ * Keys are summed in ascending order: the same input gives the same bits; nothing is read on the host (capturable).
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_ATTN_CAUSAL = 1, CPLXAMD_ATTN_ABS = 2 };
+enum { CPLXAMD_ATTN_Q_TILE = 0,              /* queries per workgroup of the forward (four waves of 32)                 */
+       CPLXAMD_ATTN_K_TILE = 1,              /* keys per LDS stage: 32 (float32) or 64 (bf16)                           */
+       CPLXAMD_ATTN_HEAD = 2,                /* the compiled head size max(E, Ev) rounds up to: 32, 64 or 128           */
+       CPLXAMD_ATTN_Q_TILES = 3,             /* ceil(L / q tile)                                                        */
+       CPLXAMD_ATTN_GRID = 4,                /* workgroups of the forward: q tiles x batch                              */
+       CPLXAMD_ATTN_LDS_BYTES = 5,           /* dynamic LDS of the forward (two stages of K and V, both planes)         */
+       CPLXAMD_ATTN_WS_BYTES = 6,            /* workspace of the backward: 4 bytes per (batch, query)                   */
+       CPLXAMD_ATTN_PLAN_FIELDS = 7 };
+typedef struct cplxamd_attn_desc {
+  int64_t L, S, E, Ev;  /* queries, keys, head size of q / k and of v / o: L, S >= 1, 1 <= E, Ev <= 128 */
+  int32_t runs;         /* 0 .. 3 batch runs, run 0 outermost */
+  int32_t flags;        /* CPLXAMD_ATTN_* bits */
+  int64_t size[3];
+  int64_t q_stride[3], k_stride[3], v_stride[3], o_stride[3], lse_stride[3];
+  int64_t dq_stride[3], dk_stride[3], dv_stride[3];     /* backward only */
+  int64_t q_rs, k_rs, v_rs, o_rs, dq_rs, dk_rs, dv_rs;  /* row strides, >= 0 (outputs: >= the row's length) */
+  double  scale;
+} cplxamd_attn_desc;    /* 320 bytes */
+int cplxamd_attn_plan(int64_t L, int64_t S, int64_t E, int64_t Ev, int64_t batch, int dtype, int64_t* plan);
+int cplxamd_attn_fwd(const void* q_r, const void* q_i, const void* k_r, const void* k_i, const void* v_r, const void* v_i,
+                     void* o_r, void* o_i, float* lse, const cplxamd_attn_desc* d, int dtype, void* stream);
+int cplxamd_attn_bwd(const void* q_r, const void* q_i, const void* k_r, const void* k_i, const void* v_r, const void* v_i,
+                     const void* o_r, const void* o_i, const void* g_r, const void* g_i, const float* lse,
+                     void* dq_r, void* dq_i, void* dk_r, void* dk_i, void* dv_r, void* dv_i, const cplxamd_attn_desc* d,
+                     int dtype, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
