@@ -243,6 +243,11 @@ SIGNATURES = {
     "cplxamd_attn_plan": [_L, _L, _L, _L, _L, _I, _P],
     "cplxamd_attn_fwd": [_P] * 10 + [_I, _P],
     "cplxamd_attn_bwd": [_P] * 18 + [_I, _P, _L, _P],
+    # still ABI 25: complex layer normalisation behind cplx.layer_norm (csrc/layer_norm.hip; the descriptor is LnDesc,
+    # the plan fills LN_PLAN_FIELDS int64)
+    "cplxamd_ln_plan": [_L, _L, _I, _I, _P],
+    "cplxamd_ln_fwd": [_P] * 8 + [_I, _P],
+    "cplxamd_ln_bwd": [_P] * 11 + [_I, _P, _L, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -288,6 +293,20 @@ class AttnDesc(ctypes.Structure):
 # fields of cplxamd_attn_plan's output (CPLXAMD_ATTN_*) and the flag bits
 ATTN_PLAN_FIELDS = ("q_tile", "k_tile", "head", "q_tiles", "grid", "lds_bytes", "ws_bytes")
 ATTN_CAUSAL, ATTN_ABS = 1, 2
+
+
+class LnDesc(ctypes.Structure):
+    """cplxamd_ln_desc: features per row, up to three runs of rows (run 0 outermost) with the strides of x, of the result
+    (backward: dx) and of the upstream gradient, the kind and eps."""
+    _fields_ = [("N", c_int64), ("runs", ctypes.c_int32), ("kind", ctypes.c_int32), ("size", c_int64 * 3),
+                ("x_stride", c_int64 * 3), ("o_stride", c_int64 * 3), ("g_stride", c_int64 * 3), ("eps", c_double)]
+
+
+# kinds (CPLXAMD_LN_WHITEN / _MODULUS), plans (CPLXAMD_LN_WAVE / _BLOCK / _STREAM) and the fields of cplxamd_ln_plan's output
+LN_KINDS = ("whiten", "modulus")
+LN_PLANS = ("wave", "block", "stream")
+LN_PLAN_FIELDS = ("plan", "threads", "rows_per_wg", "tile", "grid", "seam_wave", "seam_block", "bwd_threads",
+                  "bwd_rows_per_wg", "bwd_grid", "ws_bytes", "ws_cap", "stat_floats", "bwd_plan", "bwd_seam_block")
 
 
 class StftDesc(ctypes.Structure):

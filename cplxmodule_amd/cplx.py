@@ -1060,3 +1060,17 @@ def scaled_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.
     grouped heads raise `CplxAmdError`.  Differentiable once; the leading dims are read in place through strides."""
     from . import attention as _attention
     return _attention.scaled_dot_product_attention(query, key, value, attn_mask, dropout_p, is_causal, scale, score)
+
+
+# ---- layer normalisation: per-row whitening (or modulus normalisation) and a 2 x 2 affine map on one fused kernel
+# (cplxmodule_amd/layer_norm.py, csrc/layer_norm.hip) -------------------------------------------------------------------
+def layer_norm(input, normalized_shape, weight=None, bias=None, eps=1e-5, kind="whiten"):
+    r"""Layer normalisation of a `Cplx` tensor over its last `len(normalized_shape)` dims (one row of N complex features).
+    With c = x - mean x, `kind="whiten"` multiplies c by the inverse square root of the row's 2 x 2 covariance of
+    (Re, Im) plus eps I (the convention of the batch norm here: unit variance per plane, planes uncorrelated);
+    `"modulus"` divides by sqrt(mean |c|^2 + eps) (E|y|^2 = 1).  `weight` [2, 2, *normalized_shape] and `bias`
+    [2, *normalized_shape] (float32) apply out = W y + B per feature.  float32 and bfloat16 run one fused launch that
+    holds the row in registers, and a two-launch backward; float64 takes the composed route.  Differentiable
+    once; the leading dims are read in place through strides."""
+    from . import layer_norm as _layer_norm
+    return _layer_norm.layer_norm(input, normalized_shape, weight, bias, eps, kind)

@@ -15,3 +15,4 @@ from .casting import CplxModulus, CplxAngle  # noqa: F401
 from .extra import CplxDropout  # noqa: F401
 from .pooling import CplxMaxPool1d, CplxMaxPool2d, CplxMaxPool3d  # noqa: F401
 from .attention import CplxMultiheadAttention  # noqa: F401
+from .layernorm import CplxLayerNorm  # noqa: F401

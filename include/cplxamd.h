@@ -1612,6 +1612,60 @@ int cplxamd_attn_bwd(const void* q_r, const void* q_i, const void* k_r, const vo
                      void* dq_r, void* dq_i, void* dk_r, void* dk_i, void* dv_r, void* dv_i, const cplxamd_attn_desc* d,
                      int dtype, void* ws, int64_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Complex layer normalisation of planar tensors (cplx.layer_norm, nn.CplxLayerNorm; csrc/layer_norm.hip).
+ * New exports under ABI 25: nothing existing changes.  Per row of N complex features, with m = mean x and c = x - m:
+ *   CPLXAMD_LN_WHITEN   a = mean c_r^2 + eps, d = mean c_i^2 + eps, b = mean c_r c_i, s = sqrt(a d - b^2),
+ *                       t = s sqrt(a + d + 2 s), p = (d + s) / t, q = -b / t, r = (a + s) / t,
+ *                       y_r = p c_r + q c_i, y_i = q c_r + r c_i;            stats row: m_r, m_i, p, q, r
+ *   CPLXAMD_LN_MODULUS  v = mean |c|^2 + eps, y = c / sqrt(v);                 stats row: m_r, m_i, 1 / sqrt(v)
+ *   out_r = W00 y_r + W01 y_i + B0, out_i = W10 y_r + W11 y_i + B1 with weight [2][2][N] and bias [2][N] (float32, dense;
+ *   weight NULL: out = y; bias NULL: no bias).
+ * A row is N elements of stride 1; rows are found through up to three runs (run 0 outermost), strides in elements, the
+ * planes of a tensor sharing them; stats is dense [rows][5 or 3] float32 in the rows' enumeration order.  dtype is
+ * CPLXAMD_F32 or CPLXAMD_BF16 (float32 arithmetic and statistics, rounded once on the store) and holds for x, the result,
+ * the upstream gradient g and dx.  The moments are centred ones taken from registers, never E[x^2] - m^2.
+ * cplxamd_ln_plan is a pure function (no GPU) and fills plan[CPLXAMD_LN_PLAN_FIELDS]; cplxamd_ln_fwd is ONE launch;
+ * cplxamd_ln_bwd is one launch of persistent workgroups that writes dx (through o_stride) and per-workgroup partial
+ * parameter gradients into ws, plus one finishing launch that sums them in workgroup order into dweight [2][2][N] and
+ * dbias [2][N] (no atomics: the same input gives the same bits).  dx_r and dx_i may both be NULL (dx is not written), and
+ * so may dweight and dbias (no partials, no finishing launch, ws unused).  Every argument is checked before any launch:
+ * CPLXAMD_EINVAL (NULL pointer, bad dtype or kind, N < 1, eps negative or not finite, negative strides), CPLXAMD_ESHAPE
+ * (N beyond 2^30), CPLXAMD_EWS.  No rows: no launch, returns 0.  Nothing is read on the host (capturable).
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_LN_WHITEN = 0, CPLXAMD_LN_MODULUS = 1 };
+enum { CPLXAMD_LN_WAVE = 0, CPLXAMD_LN_BLOCK = 1, CPLXAMD_LN_STREAM = 2 };
+enum { CPLXAMD_LN_PLAN = 0,                  /* the forward's plan: CPLXAMD_LN_WAVE, _BLOCK or _STREAM                  */
+       CPLXAMD_LN_THREADS = 1,               /* threads of a forward workgroup                                          */
+       CPLXAMD_LN_ROWS_PER_WG = 2,           /* rows a forward workgroup holds at a time: 4 (wave) or 1                 */
+       CPLXAMD_LN_TILE = 3,                  /* columns the owner of a row holds in registers: 512 or 8192              */
+       CPLXAMD_LN_GRID = 4,                  /* workgroups of the forward                                               */
+       CPLXAMD_LN_SEAM_WAVE = 5,             /* the largest N of the wave plan                                          */
+       CPLXAMD_LN_SEAM_BLOCK = 6,            /* the largest N of the block plan; above: stream                          */
+       CPLXAMD_LN_BWD_THREADS = 7,           /* threads of a backward workgroup                                         */
+       CPLXAMD_LN_BWD_ROWS_PER_WG = 8,       /* rows a backward workgroup holds at a time                               */
+       CPLXAMD_LN_BWD_GRID = 9,              /* persistent workgroups of the backward                                   */
+       CPLXAMD_LN_WS_BYTES = 10,             /* workspace of the backward: grid x 6 x N floats                          */
+       CPLXAMD_LN_WS_CAP = 11,               /* what the workspace never exceeds (long rows: fewer workgroups)          */
+       CPLXAMD_LN_STAT_FLOATS = 12,          /* floats per row of stats: 5 or 3                                         */
+       CPLXAMD_LN_BWD_PLAN = 13,             /* the backward's plan: its block plan ends at the seam below              */
+       CPLXAMD_LN_BWD_SEAM_BLOCK = 14,       /* the largest N of the backward's block plan                              */
+       CPLXAMD_LN_PLAN_FIELDS = 15 };
+typedef struct cplxamd_ln_desc {
+  int64_t N;            /* features per row, >= 1 */
+  int32_t runs;         /* 0 .. 3 runs of rows, run 0 outermost */
+  int32_t kind;         /* CPLXAMD_LN_WHITEN or CPLXAMD_LN_MODULUS */
+  int64_t size[3];
+  int64_t x_stride[3], o_stride[3], g_stride[3];   /* o: the result (forward) or dx (backward); g: backward only */
+  double  eps;
+} cplxamd_ln_desc;      /* 120 bytes */
+int cplxamd_ln_plan(int64_t rows, int64_t N, int kind, int dtype, int64_t* plan);
+int cplxamd_ln_fwd(const void* x_r, const void* x_i, const float* weight, const float* bias, void* y_r, void* y_i,
+                   float* stats, const cplxamd_ln_desc* d, int dtype, void* stream);
+int cplxamd_ln_bwd(const void* x_r, const void* x_i, const void* g_r, const void* g_i, const float* weight,
+                   const float* stats, void* dx_r, void* dx_i, float* dweight, float* dbias, const cplxamd_ln_desc* d,
+                   int dtype, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
