@@ -248,6 +248,10 @@ SIGNATURES = {
     "cplxamd_ln_plan": [_L, _L, _I, _I, _P],
     "cplxamd_ln_fwd": [_P] * 8 + [_I, _P],
     "cplxamd_ln_bwd": [_P] * 11 + [_I, _P, _L, _P],
+    # still ABI 25: the first-order recurrence with a coefficient per step behind cplx.linear_recurrence / cumsum / cumprod
+    # (csrc/scan.hip; the descriptor is ScanDesc, the plan fills SCAN_PLAN_FIELDS int64)
+    "cplxamd_scan_plan": [_P, _I, _I, _P],
+    "cplxamd_scan": [_P] * 9 + [_I, _I, _P, _L, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -307,6 +311,21 @@ LN_KINDS = ("whiten", "modulus")
 LN_PLANS = ("wave", "block", "stream")
 LN_PLAN_FIELDS = ("plan", "threads", "rows_per_wg", "tile", "grid", "seam_wave", "seam_block", "bwd_threads",
                   "bwd_rows_per_wg", "bwd_grid", "ws_bytes", "ws_cap", "stat_floats", "bwd_plan", "bwd_seam_block")
+
+
+class ScanDesc(ctypes.Structure):
+    """cplxamd_scan_desc: steps per row, the forced segment count, the element strides of a, x and the result along time,
+    up to three batch runs (run 0 outermost) with the strides of a, x, h0 and the result, and the flags."""
+    _fields_ = [("n", c_int64), ("force_segments", c_int64), ("a_es", c_int64), ("x_es", c_int64), ("y_es", c_int64),
+                ("runs", ctypes.c_int32), ("flags", ctypes.c_int32), ("size", c_int64 * 3), ("a_stride", c_int64 * 3),
+                ("x_stride", c_int64 * 3), ("h_stride", c_int64 * 3), ("y_stride", c_int64 * 3)]
+
+
+# plans (CPLXAMD_SCAN_ROW / _COLUMN), the fields of cplxamd_scan_plan's output (CPLXAMD_SCAN_*) and the flag bits
+SCAN_PLANS = ("row", "column")
+SCAN_PLAN_FIELDS = ("chunk", "tile", "tiles", "segments", "seg_len", "window", "units", "lds_bytes", "threads", "grid",
+                    "ws_bytes")
+SCAN_REVERSE, SCAN_CONJ, SCAN_LAG = 1, 2, 4
 
 
 class StftDesc(ctypes.Structure):

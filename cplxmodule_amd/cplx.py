@@ -1074,3 +1074,38 @@ def layer_norm(input, normalized_shape, weight=None, bias=None, eps=1e-5, kind="
     once; the leading dims are read in place through strides."""
     from . import layer_norm as _layer_norm
     return _layer_norm.layer_norm(input, normalized_shape, weight, bias, eps, kind)
+
+
+# ---- the first-order recurrence with a coefficient per step, and the running sum and product, on one time-parallel scan
+# kernel (cplxmodule_amd/scan.py, csrc/scan.hip) -------------------------------------------------------------------------
+def linear_recurrence(a, x, h0=None, reverse=False):
+    r"""The linear recurrence h[t] = a[t] h[t - 1] + x[t] along the last dim, h[-1] = `h0` (default 0): the gated /
+    selective diagonal state-space recurrence, the time-varying one-pole filter (|a| = 1: a phase accumulator; a[t] = 0: a
+    reset).  `a` and `x` [..., T] are each a `Cplx` or a real tensor (a null imaginary plane: never read); the last dim of
+    `a` may be 1; `h0` broadcasts to the batch shape.  All-real operands give a real tensor, else a `Cplx`, dense in `x`'s
+    memory order, in the operands' dtype (float32, bfloat16 -- float32 arithmetic and state, one rounding -- or float64, on
+    the device).  `reverse=True` runs h[t] = a[t] h[t + 1] + x[t] from the last sample.  Leading dims broadcast by
+    torch's rules and are read in place; there is no `dim`: a [B, T, D] model passes `.transpose(-1, -2)` views and
+    transposes the result back, which the kernel serves with lanes along D.  One launch (two for long rows
+    with few rows), parallel in time: chunks of 16 steps in registers, their maps h -> P h + s composed in order, each
+    chunk rerun from its true entering state.  Deterministic, capturable in a hipGraph, differentiable to any order in
+    a, x and h0 (the adjoint is the same kernel; da and dh0 are torch products, not the hot path).
+    Numerical limit: the kernel forms products of up to `scan.plan(...)["window"]` consecutive coefficients (4096 in a
+    row, 64 in the column layout, one segment when a row is cut).  For |a| <= 1 these are harmless; for sustained |a| > 1
+    such a product can overflow where the sequential value is still finite.  This is not special-cased."""
+    from . import scan as _scan
+    return _scan.linear_recurrence(a, x, h0, reverse)
+
+
+def cumsum(x, reverse=False):
+    r"""The running sum along the last dim of a `Cplx` or a real tensor, on `linear_recurrence`'s kernel with a = 1 (a
+    stride-0 view: no plane of ones).  Operands, layouts, dtypes and derivatives as `linear_recurrence`."""
+    from . import scan as _scan
+    return _scan.cumsum(x, reverse)
+
+
+def cumprod(a, reverse=False):
+    r"""The running product along the last dim of a `Cplx` or a real tensor, on `linear_recurrence`'s kernel with a null
+    x and h0 = 1.  Operands, layouts, dtypes and derivatives as `linear_recurrence`."""
+    from . import scan as _scan
+    return _scan.cumprod(a, reverse)

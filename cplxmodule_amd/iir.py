@@ -306,15 +306,16 @@ def _section(xr, xi, cr, ci, zr, zi, D, cx):
     return yr, yi, fr, fi
 
 
-def _operands(fn, named):
-    """planes of every operand, with the checks the two functions share -> {name: (re, im)}"""
+def _operands(fn, named, scalars=()):
+    """planes of every operand, with the checks the signal functions share -> {name: (re, im)}; the operands named in
+    `scalars` may be 0-d"""
     out, first = {}, None
     for name, v in named:
         if v is None:
             out[name] = (None, None)
             continue
         pr, pi = planes(v, name, fn)
-        if pr.dim() == 0:
+        if pr.dim() == 0 and name not in scalars:
             raise ValueError(f"{fn}: `{name}` is 0-d: there is no dim to filter along")
         if first is None:
             first = (name, pr.dtype)

@@ -1666,6 +1666,64 @@ int cplxamd_ln_bwd(const void* x_r, const void* x_i, const void* g_r, const void
                    const float* stats, void* dx_r, void* dx_i, float* dweight, float* dbias, const cplxamd_ln_desc* d,
                    int dtype, void* ws, int64_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * The first-order linear recurrence with a coefficient per step, along the last dim (cplx.linear_recurrence, cplx.cumsum,
+ * cplx.cumprod; csrc/scan.hip).  New exports under ABI 25: nothing existing changes.  For every row of n steps, in
+ * processing order p = 0 .. n - 1 (step p is sample p, or sample n - 1 - p with CPLXAMD_SCAN_REVERSE):
+ *   h[p] = c[p] h[p - 1] + x[p],   h[-1] = h0 (zero when h_r is NULL)
+ * with c[p] the coefficient of step p, conjugated with CPLXAMD_SCAN_CONJ.  With CPLXAMD_SCAN_LAG c[p] is the coefficient
+ * of step p - 1, the position the state comes from, and step 0 has none: nothing enters it and no address outside a is
+ * formed (h0 must be NULL with this flag).  Flipping all three flags gives the adjoint of a run.
+ * Sample j of row r = (i0, i1, i2) of a lies at a_r / a_i [sum_q i_q a_stride[q] + j a_es]; x and the result likewise;
+ * h0 of the row at h_r / h_i [sum_q i_q h_stride[q]].  Strides are in elements and may be 0 (a shared coefficient row, a
+ * coefficient that is constant along time: a_es = 0); the planes of an operand share them.  x_r NULL is a null input;
+ * a_i, x_i, h_i NULL are planes of zeros that are never read.  `cplx` = 0: real arithmetic, every imaginary pointer NULL.
+ * dtype (of every plane): F32, BF16 (float32 arithmetic and state, rounded once on the store) or F64.
+ * A chunk of CHUNK consecutive steps stays in registers: it is run from zero state for its coefficient product P and
+ * local final state s, the maps (P, s) are composed in order, (P2, s2) o (P1, s1) = (P2 P1, P2 s1 + s2), and the chunk is
+ * run again from its true entering state and stored: the stored values are the sequential recurrence's.
+ * cplxamd_scan_plan is a pure function (no GPU) of the descriptor: CPLXAMD_SCAN_ROW when y_es = 1 (a chunk per thread, a
+ * tile of 256 CHUNK steps of one row per workgroup), CPLXAMD_SCAN_COLUMN when y_es != 1 and the innermost run has stride 1
+ * in x and the result and 1 or 0 in a (lanes along that run, 64 channels per workgroup, a tile of 4 CHUNK steps);
+ * any other layout is CPLXAMD_EINVAL (the caller copies).  Fewer than 256 units (rows, or rows times channel groups) of at
+ * least 4 tiles are cut into SEGMENTS segments of whole tiles, up to 1024 workgroups, and the call is two launches: one
+ * map per (unit, segment) from zero state into ws, then every workgroup composes the maps before its own in order and
+ * runs its segment.  force_segments > 0 cuts into that many segments (at most n) of ceil(n / segments) steps instead.
+ * NUMERICAL LIMIT: the products P span up to WINDOW consecutive coefficients (one tile, or one segment when cut).  For
+ * |a| <= 1 an underflow to 0 is the right limit; for sustained |a| > 1 a product can overflow where the sequential value
+ * is still finite (a zero state times an infinite product, or a later a = 0).  This is not special-cased.
+ * cplxamd_scan checks before any launch: CPLXAMD_EINVAL (NULL a_r / y_r / d, a plane that `cplx` forbids or a missing
+ * one, dtype, unknown flags, h0 with LAG, negative sizes or strides, a layout without a plan), CPLXAMD_ESHAPE (n above
+ * 2^40, more than 2^31 - 1 workgroups), CPLXAMD_EWS (ws below WS_BYTES).  No rows: returns 0.  No atomics: reruns give the
+ * same bits.  Nothing is read on the host (capturable).
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_SCAN_ROW = 0, CPLXAMD_SCAN_COLUMN = 1 };
+enum { CPLXAMD_SCAN_REVERSE = 1, CPLXAMD_SCAN_CONJ = 2, CPLXAMD_SCAN_LAG = 4 };
+enum { CPLXAMD_SCAN_CHUNK = 0,           /* steps per chunk (L): 16, or 8 for F64                                       */
+       CPLXAMD_SCAN_TILE,                /* steps per tile: 256 CHUNK (row) or 4 CHUNK (column)                         */
+       CPLXAMD_SCAN_TILES,               /* tiles per row                                                               */
+       CPLXAMD_SCAN_SEGMENTS,
+       CPLXAMD_SCAN_SEG_LEN,
+       CPLXAMD_SCAN_WINDOW,              /* consecutive coefficients whose product is formed                            */
+       CPLXAMD_SCAN_UNITS,               /* rows (row plan) or rows times groups of 64 channels (column plan)           */
+       CPLXAMD_SCAN_LDS_BYTES,
+       CPLXAMD_SCAN_THREADS,
+       CPLXAMD_SCAN_GRID,                /* UNITS * SEGMENTS                                                            */
+       CPLXAMD_SCAN_WS_BYTES,            /* UNITS (SEGMENTS - 1) maps of 2 or 4 compute-type words, x 64 lanes (column) */
+       CPLXAMD_SCAN_PLAN_FIELDS };
+typedef struct cplxamd_scan_desc {
+  int64_t n;              /* steps per row, >= 1 */
+  int64_t force_segments; /* 0: the plan chooses */
+  int64_t a_es, x_es, y_es; /* element strides along time; a_es, x_es >= 0, y_es >= 1 */
+  int32_t runs;           /* 0 .. 3 batch runs, run 0 outermost */
+  int32_t flags;          /* CPLXAMD_SCAN_REVERSE | CPLXAMD_SCAN_CONJ | CPLXAMD_SCAN_LAG */
+  int64_t size[3], a_stride[3], x_stride[3], h_stride[3], y_stride[3];
+} cplxamd_scan_desc;      /* 168 bytes */
+int cplxamd_scan_plan(const cplxamd_scan_desc* d, int dtype, int cplx, int64_t* out);
+int cplxamd_scan(const void* a_r, const void* a_i, const void* x_r, const void* x_i, const void* h_r, const void* h_i,
+                 void* y_r, void* y_i, const cplxamd_scan_desc* d, int cplx, int dtype, void* ws, int64_t ws_bytes,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
