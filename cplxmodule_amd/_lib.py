@@ -252,6 +252,11 @@ SIGNATURES = {
     # (csrc/scan.hip; the descriptor is ScanDesc, the plan fills SCAN_PLAN_FIELDS int64)
     "cplxamd_scan_plan": [_P, _I, _I, _P],
     "cplxamd_scan": [_P] * 9 + [_I, _I, _P, _L, _P],
+    # still ABI 25: the polyphase filter bank behind cplx.pfb_analysis / pfb_synthesis (csrc/pfb.hip; the descriptor is
+    # PfbDesc, the plan fills PFB_PLAN_FIELDS int64)
+    "cplxamd_pfb_plan": [_P, _I, _P],
+    "cplxamd_pfb_analysis": [_P] * 6 + [_I, _P],
+    "cplxamd_pfb_synthesis": [_P] * 6 + [_I, _P, _L, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -326,6 +331,20 @@ SCAN_PLANS = ("row", "column")
 SCAN_PLAN_FIELDS = ("chunk", "tile", "tiles", "segments", "seg_len", "window", "units", "lds_bytes", "threads", "grid",
                     "ws_bytes")
 SCAN_REVERSE, SCAN_CONJ, SCAN_LAG = 1, 2, 4
+
+
+class PfbDesc(ctypes.Structure):
+    """cplxamd_pfb_desc: channels, taps per branch, hop, frames, samples per row, the element stride of the analysis
+    input, the frame and channel strides of the synthesis input, up to three batch runs (run 0 outermost) with the
+    strides of the signal and of the spectrum."""
+    _fields_ = [("channels", c_int64), ("taps", c_int64), ("hop", c_int64), ("frames", c_int64), ("length", c_int64),
+                ("sig_es", c_int64), ("spec_fs", c_int64), ("spec_es", c_int64), ("runs", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("size", c_int64 * 3), ("sig_stride", c_int64 * 3), ("spec_stride", c_int64 * 3)]
+
+
+# plans (CPLXAMD_PFB_STAGED / _DIRECT) and the fields of cplxamd_pfb_plan's output (CPLXAMD_PFB_*)
+PFB_PLANS = ("staged", "direct")
+PFB_PLAN_FIELDS = ("frames_per_tile", "tiles", "vectors_per_workgroup", "span", "lds_bytes", "threads", "grid", "ws_bytes")
 
 
 class StftDesc(ctypes.Structure):

@@ -871,6 +871,34 @@ def czt_points(m, w=None, a=1 + 0j):
     return _czt.czt_points(m, w, a)
 
 
+# ---- polyphase filter banks: a channelizer and its adjoint on one fused kernel (cplxmodule_amd/pfb.py, csrc/pfb.hip) ------
+def pfb_analysis(x, h, n_channels, hop=None):
+    r"""Polyphase analysis filter bank (channelizer) along the last dim: with M = `n_channels` (a power of two, 2 .. 4096)
+    and K = len(h) = P M real prototype taps (1 <= P <= 64), frame f starts at sample f hop and
+    y[f, k] = sum_{n < K} h[n] x[f hop + n] e^{-2 pi i k n / M}: the bins 0, P, 2 P, ... of the K-point DFT of the windowed
+    frame, computed as an M-point FFT of the P-fold folded frame.  `hop` defaults to M (critically sampled), 1 <= hop <= K;
+    the phase reference is the start of each frame, whatever the hop.  `x` [..., T] is a `Cplx` or a real tensor (a null
+    imaginary plane: never allocated or read) of float32 or bfloat16 (float32 arithmetic, one rounding) on the device,
+    T >= K; `h` is a real float32 1-d tensor (bfloat16 is widened once) and gets no gradient.  -> `Cplx`
+    [..., F, M], F = (T - K) // hop + 1, dense; there is no padding and samples behind the last frame are not read.
+    Leading dims are batch and are read in place.  One launch, no workspace: a workgroup stages the samples of a tile of
+    frames through LDS once (long filters: reads them from global memory).  Deterministic, capturable in a hipGraph,
+    differentiable to any order in `x`: the backward is `pfb_synthesis` with the same taps."""
+    from . import pfb as _pfb
+    return _pfb.pfb_analysis(x, h, n_channels, hop)
+
+
+def pfb_synthesis(y, g, hop=None, length=None):
+    r"""Polyphase synthesis filter bank, the adjoint of `pfb_analysis`: for a `Cplx` y [..., F, M] and K = len(g) = P M real
+    taps, out[t] = sum_f g[t - f hop] sum_k y[f, k] e^{+2 pi i k (t - f hop) / M} over the frames with 0 <= t - f hop < K,
+    -> `Cplx` [..., length].  `length` defaults to (F - 1) hop + K and may be larger (the tail is zero); `hop` defaults to
+    M.  Unnormalised: there is no 1 / M, the taps carry it.  The M-point inverse transforms go into a float32 workspace
+    from torch's allocator and one gather pass sums each output's frames in ascending order: no atomics, the same bits on
+    every run.  Dtypes, layouts, capture and derivatives as `pfb_analysis`, whose kernel is its backward."""
+    from . import pfb as _pfb
+    return _pfb.pfb_synthesis(y, g, hop, length)
+
+
 def upfirdn(h, x, up=1, down=1):
     r"""Upsample by `up`, FIR filter, downsample by `down` along the last dim, with the argument order and the result of
     `scipy.signal.upfirdn` (`mode="constant"`): y[n] = sum_k h[k] xu[n down - k] where xu[i up] = x[i] and zero

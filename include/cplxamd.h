@@ -1724,6 +1724,59 @@ int cplxamd_scan(const void* a_r, const void* a_i, const void* x_r, const void* 
                  void* y_r, void* y_i, const cplxamd_scan_desc* d, int cplx, int dtype, void* ws, int64_t ws_bytes,
                  void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * The polyphase filter bank along the last dim (cplx.pfb_analysis, cplx.pfb_synthesis; csrc/pfb.hip).  New exports under
+ * ABI 25: nothing existing changes.  M channels (a power of two, 2 .. 4096), P taps per branch (1 .. 64), K = P M real
+ * taps, a frame every `hop` samples (1 .. K), the phase referred to the start of the frame:
+ *   analysis    y[f][k] = sum_{n < K} h[n] x[f hop + n] e^{-2 pi i k n / M}
+ *                       = FFT_M(u[f])[k],   u[f][r] = sum_{p < P} h[p M + r] x[f hop + p M + r]       f < frames, k < M
+ *   synthesis   o[t] = sum_{f ascending, 0 <= t - f hop < K} g[t - f hop] v[f][(t - f hop) mod M],     t < length
+ *               v[f][m] = sum_k y[f][k] e^{+2 pi i k m / M}    (unnormalised: the taps carry any 1 / M)
+ * which are each other's adjoints.  Sample j of row r = (i0, i1, i2) of the analysis input lies at
+ * x_r / x_i [sum_q i_q sig_stride[q] + j sig_es]; entry (f, k) of the synthesis input at y_r / y_i [sum_q i_q
+ * spec_stride[q] + f spec_fs + k spec_es].  The RESULTS are dense, rows in run order: y [rows][frames][M], o [rows][length];
+ * the descriptor's strides of a result are not read.  A NULL x_i is a plane of zeros that is never read; a NULL o_i asks
+ * for the real plane only.  Planes are F32 or BF16 (float32 arithmetic, one rounding at the store); the taps are float32.
+ * Analysis needs (frames - 1) hop + K <= length and reads no sample behind the last frame; it is one launch without a
+ * workspace.  A workgroup owns FRAMES_PER_TILE consecutive frames of one row and transforms VECTORS of them at a time:
+ * CPLXAMD_PFB_STAGED stages the tile's (FRAMES_PER_TILE - 1) hop + K samples through LDS once and forms u from there;
+ * CPLXAMD_PFB_DIRECT (that span, the transform and its twiddles exceed 160 KiB) forms u from global memory.
+ * Synthesis is two launches: the inverse transforms into ws (float32 [planes][rows][frames][M], WS_BYTES) and a gather
+ * that sums each output's frames in ascending order: no atomics, reruns give the same bits.
+ * cplxamd_pfb_plan is a pure function (no GPU) of the descriptor; `cplx`: two signal planes (1) or one (0).  It returns
+ * the plan.  The entry points check before any launch: CPLXAMD_EINVAL (NULL x_r / h / y_r / d, an imaginary plane without
+ * its real one, dtype, a field out of range, frames that do not fit the length), CPLXAMD_ESHAPE (more than 2^31 - 1
+ * workgroups or entries beyond 64 bits), CPLXAMD_EWS.  No rows or no frames: analysis returns 0; synthesis clears o.
+ * Nothing is read on the host (capturable).
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_PFB_STAGED = 0, CPLXAMD_PFB_DIRECT = 1 };
+enum { CPLXAMD_PFB_FRAMES_PER_TILE = 0,  /* frames a workgroup owns                                                     */
+       CPLXAMD_PFB_TILES,                /* tiles per row                                                               */
+       CPLXAMD_PFB_VECTORS,              /* frames transformed at a time by one workgroup (> 1: packed)                 */
+       CPLXAMD_PFB_SPAN,                 /* samples per plane staged by a full tile (0: direct)                         */
+       CPLXAMD_PFB_LDS_BYTES,
+       CPLXAMD_PFB_THREADS,
+       CPLXAMD_PFB_GRID,                 /* rows * TILES                                                                */
+       CPLXAMD_PFB_WS_BYTES,             /* synthesis: the inverse transforms of every frame                            */
+       CPLXAMD_PFB_PLAN_FIELDS };
+typedef struct cplxamd_pfb_desc {
+  int64_t channels;     /* M */
+  int64_t taps;         /* P, per branch; K = P M */
+  int64_t hop;
+  int64_t frames;
+  int64_t length;       /* samples per row of the signal (analysis: read; synthesis: written) */
+  int64_t sig_es;       /* element stride of the analysis input along time, >= 0 */
+  int64_t spec_fs, spec_es; /* frame and channel strides of the synthesis input, >= 0 */
+  int32_t runs;         /* 0 .. 3 batch runs, run 0 outermost */
+  int32_t flags;        /* reserved: 0 */
+  int64_t size[3], sig_stride[3], spec_stride[3];
+} cplxamd_pfb_desc;     /* 144 bytes */
+int cplxamd_pfb_plan(const cplxamd_pfb_desc* d, int cplx, int64_t* out);
+int cplxamd_pfb_analysis(const void* x_r, const void* x_i, const void* h, void* y_r, void* y_i, const cplxamd_pfb_desc* d,
+                         int dtype, void* stream);
+int cplxamd_pfb_synthesis(const void* y_r, const void* y_i, const void* g, void* o_r, void* o_i, const cplxamd_pfb_desc* d,
+                          int dtype, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
