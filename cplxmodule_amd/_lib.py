@@ -257,6 +257,10 @@ SIGNATURES = {
     "cplxamd_pfb_plan": [_P, _I, _P],
     "cplxamd_pfb_analysis": [_P] * 6 + [_I, _P],
     "cplxamd_pfb_synthesis": [_P] * 6 + [_I, _P, _L, _P],
+    # still ABI 25: the multi-state diagonal state-space scan behind cplx.ssm_scan (csrc/ssm.hip; the descriptor is
+    # SsmDesc, the plan fills SSM_PLAN_FIELDS int64)
+    "cplxamd_ssm_plan": [_L, _L, _L, _I, _I, _I, _P],
+    "cplxamd_ssm_scan": [_P] * 16 + [_I, _I, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -331,6 +335,22 @@ SCAN_PLANS = ("row", "column")
 SCAN_PLAN_FIELDS = ("chunk", "tile", "tiles", "segments", "seg_len", "window", "units", "lds_bytes", "threads", "grid",
                     "ws_bytes")
 SCAN_REVERSE, SCAN_CONJ, SCAN_LAG = 1, 2, 4
+
+
+class SsmDesc(ctypes.Structure):
+    """cplxamd_ssm_desc: steps per row, states, the element strides of a, b, c along time and of a, b, c, h0 and the final
+    state along the states, up to three batch runs (run 0 outermost) with the strides of a, b, c, x, dt, h0, the result
+    and the final state, and the flags."""
+    _fields_ = [("n", c_int64), ("states", c_int64), ("a_es", c_int64), ("b_es", c_int64), ("c_es", c_int64),
+                ("a_ns", c_int64), ("b_ns", c_int64), ("c_ns", c_int64), ("h_ns", c_int64), ("f_ns", c_int64),
+                ("runs", ctypes.c_int32), ("flags", ctypes.c_int32), ("size", c_int64 * 3), ("a_stride", c_int64 * 3),
+                ("b_stride", c_int64 * 3), ("c_stride", c_int64 * 3), ("x_stride", c_int64 * 3), ("dt_stride", c_int64 * 3),
+                ("h_stride", c_int64 * 3), ("y_stride", c_int64 * 3), ("f_stride", c_int64 * 3)]
+
+
+# the fields of cplxamd_ssm_plan's output (CPLXAMD_SSM_*) and the flag bits
+SSM_PLAN_FIELDS = ("chunk", "tile", "tiles", "group", "lds_bytes", "threads", "grid", "window")
+SSM_REVERSE, SSM_CONJ, SSM_LAG, SSM_DT_OUT = 1, 2, 4, 8
 
 
 class PfbDesc(ctypes.Structure):

@@ -1125,6 +1125,35 @@ def linear_recurrence(a, x, h0=None, reverse=False):
     return _scan.linear_recurrence(a, x, h0, reverse)
 
 
+def ssm_scan(a, b, c, x, dt=None, h0=None, return_state=False, reverse=False):
+    r"""The diagonal state-space layer with N states per channel along the last dim, fused: the states stay on chip and
+    only y is written.
+
+        h[n, t] = a[n, t] h[n, t - 1] + b[n, t] x[t],   y[t] = sum_n c[n, t] h[n, t],   h[n, -1] = `h0`[n] (default 0)
+
+    `x` [..., T]; `a`, `b`, `c` [..., N, T], or [..., N, 1] for values constant in time; `h0` [..., N]; each a `Cplx` or a
+    real tensor (a null imaginary plane: never allocated or read).  With `dt` (a REAL tensor [..., T]) `a` must be
+    [..., N, 1], the continuous poles: the kernel forms exp(dt[t] a[n]) and dt[t] x[t] in registers, with `cplx.exp`'s
+    device functions, and stores neither.  `reverse=True` runs from the last sample.  1 <= N <= 256.
+    Returns y [..., T], dense, real only when every operand is real; with `return_state=True` (y, hT), hT [..., N] the
+    state after the last processed step: passed as `h0` of the next block it continues the scan.  float32 and bfloat16 run
+    the kernel (bf16: float32 arithmetic and state, y and hT rounded once); float64 takes `ssm.composed` -- torch products
+    and `linear_recurrence` -- which is also what differentiates to any order.  Empty T or batch: empties, no launch.
+    Leading dims (before the last dim of x / dt / h0, before the last two of a / b / c) broadcast by torch's rules and are
+    read in place through strides, stride 0 included: `b`, `c` [B, 1, N, T] against `x` [B, D, T] are not copied.  Time
+    must have stride 1: an operand whose time dim is strided costs one copy.  There is NO column ([B, T, D]) plan yet,
+    and rows are not cut into segments: a few long rows run on a few workgroups (both are DESIGN 29's follow-ups).
+    Gradients: dx and dh0 come from the same kernel (b and c swapped, every flag flipped).  The gradients of a, b, c and
+    dt are formed only when asked for, by recomputing the [..., N, T] states with `linear_recurrence`'s kernel inside the
+    backward and torch products on them: that allocates N times the size of x and is not the hot path (a fused
+    parameter-gradient kernel is the follow-up).  The backward is not differentiable: use `ssm.composed` for that.
+    Numerical limit, as `linear_recurrence`'s: the kernel forms products of up to `ssm.plan(...)["window"]` (4096)
+    consecutive coefficients.  For |a| <= 1 these are harmless; for sustained |a| > 1 such a product can overflow where
+    the sequential value is still finite.  This is not special-cased."""
+    from . import ssm as _ssm
+    return _ssm.ssm_scan(a, b, c, x, dt, h0, return_state, reverse)
+
+
 def cumsum(x, reverse=False):
     r"""The running sum along the last dim of a `Cplx` or a real tensor, on `linear_recurrence`'s kernel with a = 1 (a
     stride-0 view: no plane of ones).  Operands, layouts, dtypes and derivatives as `linear_recurrence`."""

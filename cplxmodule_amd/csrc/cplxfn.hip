@@ -34,7 +34,7 @@ constexpr int kFT = 256;
 // |x| past which tanh x rounds to +-1 in float32 (1 - tanh 11 = 5.5e-10 < 2^-25) and e^{-2|x|} is negligible next to 1
 constexpr float kSat = 11.0f;
 
-struct CF { float re, im; };
+#include "cexp.h"                                         // CF and f_exp, shared with csrc/ssm.hip
 
 // (cosh t, sinh t) from one exponential
 __device__ __forceinline__ void chsh(float t, float& c, float& s) {
@@ -64,17 +64,6 @@ __device__ __forceinline__ void chsh_mul(float t, float p, float q, float& cp, f
     cp = (hh * p) * h;
     sq = (copysignf(hh, t) * q) * h;
   }
-}
-
-__device__ __forceinline__ CF f_exp(float x, float y) {
-  float s, c;
-  sincosf(y, &s, &c);
-  if (x > 88.0f) {    // e^x overflows at 88.72, e^x cos y need not
-    const float h = expf(0.5f * x);
-    return {(h * c) * h, (h * s) * h};
-  }
-  const float e = expf(x);
-  return {e * c, e * s};
 }
 
 __device__ __forceinline__ CF f_log(float x, float y) {

@@ -1777,6 +1777,64 @@ int cplxamd_pfb_analysis(const void* x_r, const void* x_i, const void* h, void* 
 int cplxamd_pfb_synthesis(const void* y_r, const void* y_i, const void* g, void* o_r, void* o_i, const cplxamd_pfb_desc* d,
                           int dtype, void* ws, int64_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * The diagonal state-space scan with `states` states per row, along the last dim (cplx.ssm_scan; csrc/ssm.hip).  New
+ * exports under ABI 25: nothing existing changes.  For every row of n steps, in processing order p = 0 .. n - 1 (step p
+ * is sample p, or sample n - 1 - p with CPLXAMD_SSM_REVERSE), and every state s < states:
+ *   h[s][p] = A[s][p] h[s][p - 1] + b[s][p] X[p],   h[s][-1] = h0[s] (zero when h_r is NULL)
+ *   y[p]    = sum_s c[s][p] h[s][p]                 f[s] = h[s][n - 1]  (written when f_r is given)
+ * dt NULL: A[s][p] = a[s][p] and X = x.  dt given (a real plane; a_es must be 0: a holds the continuous poles):
+ * A[s][p] = exp(dt[p] a[s]) and X[p] = dt[p] x[p], both formed in registers, with expf / sincosf (the device functions
+ * of cplx.exp's kernel), never stored.  CPLXAMD_SSM_CONJ conjugates a, b and c on load.  With CPLXAMD_SSM_LAG the
+ * coefficient of step p is that of step p - 1, and so is its dt; step 0 has none: h0 enters it unscaled and no address
+ * outside a or dt is formed.  With CPLXAMD_SSM_DT_OUT dt[p] scales y[p] on the store instead of x[p] on the load.
+ * THE ADJOINT: for y = run(a, b, c, x, dt, h0) and incoming gradients g (of y) and gf (of f), autograd's convention,
+ *   run(a, c, b, g, dt, gf) with all four flags flipped  ->  y' = dL/dx,  f' = lambda[.][0],  dL/dh0 = conj(A[.][0]) f'.
+ * Sample j of state s of row r = (i0, i1, i2) of a lies at a_r / a_i [sum_q i_q a_stride[q] + s a_ns + j a_es]; b and c
+ * likewise; x, dt and y at [sum_q i_q *_stride[q] + j] (time has stride 1 in them); h0 and f at [sum_q i_q *_stride[q] +
+ * s *_ns].  Strides are in elements and may be 0 (b and c shared by the rows of a batch entry; a_es = 0: one coefficient
+ * per state).  A NULL imaginary plane is a plane of zeros that is never read; cplx = 0: every operand is real and the
+ * one-plane instances run.  dtype (of the planes of a, b, c, x, dt and y): F32 or BF16 (float32 arithmetic and state; y
+ * rounded once).  The state planes h0 and f are in the COMPUTE type, float32, whatever the dtype (as cplxamd_iir's
+ * zi and zf): the adjoint's final state is a factor of dL/dh0 and must not be rounded before that product.
+ * a_es, b_es, c_es are 0 or 1: a time dim that is strided otherwise is the caller's copy.
+ * A workgroup of 256 threads walks one row's tiles of 256 CHUNK steps; a thread keeps x, dt and the accumulators of y of
+ * CHUNK steps in registers; the states go by in groups of GROUP with one barrier each; the carried states go from tile
+ * to tile through LDS.  1 <= states <= 256.  Rows are not cut into segments.
+ * NUMERICAL LIMIT, as cplxamd_scan's: products of up to WINDOW consecutive coefficients are formed; for |A| <= 1 an
+ * underflow to 0 is the right limit; for sustained |A| > 1 a product can overflow where the sequential value is finite.
+ * cplxamd_ssm_plan is a pure function (no GPU); time_varying: the coefficient varies along time (a_es != 0, or dt given).
+ * Both check before any launch: CPLXAMD_EINVAL (a NULL plane that is required, a plane that `cplx` forbids, f_i
+ * without f_r, dtype, states outside 1 .. 256, unknown flags, negative sizes or strides, a time stride above 1, dt with
+ * a_es != 0),
+ * CPLXAMD_ESHAPE (n above 2^40, more than 2^31 - 1 rows).  No rows or n = 0: returns 0.  No atomics, no workspace:
+ * reruns give the same bits.  Nothing is read on the host (capturable).
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_SSM_REVERSE = 1, CPLXAMD_SSM_CONJ = 2, CPLXAMD_SSM_LAG = 4, CPLXAMD_SSM_DT_OUT = 8 };
+enum { CPLXAMD_SSM_CHUNK = 0,            /* steps per chunk (L): 16                                                     */
+       CPLXAMD_SSM_TILE,                 /* steps per tile: 256 CHUNK                                                   */
+       CPLXAMD_SSM_TILES,                /* tiles per row                                                               */
+       CPLXAMD_SSM_GROUP,                /* states per barrier: 4, or 2 for complex operands with a time-varying A      */
+       CPLXAMD_SSM_LDS_BYTES,
+       CPLXAMD_SSM_THREADS,
+       CPLXAMD_SSM_GRID,                 /* rows                                                                        */
+       CPLXAMD_SSM_WINDOW,               /* consecutive coefficients whose product is formed                            */
+       CPLXAMD_SSM_PLAN_FIELDS };
+typedef struct cplxamd_ssm_desc {
+  int64_t n;              /* steps per row, >= 0 */
+  int64_t states;         /* 1 .. 256 */
+  int64_t a_es, b_es, c_es; /* element strides along time, 0 or 1 */
+  int64_t a_ns, b_ns, c_ns, h_ns, f_ns; /* element strides along the states, >= 0 */
+  int32_t runs;           /* 0 .. 3 batch runs, run 0 outermost */
+  int32_t flags;          /* CPLXAMD_SSM_REVERSE | _CONJ | _LAG | _DT_OUT */
+  int64_t size[3], a_stride[3], b_stride[3], c_stride[3], x_stride[3], dt_stride[3], h_stride[3], y_stride[3],
+      f_stride[3];
+} cplxamd_ssm_desc;       /* 304 bytes */
+int cplxamd_ssm_plan(int64_t n, int64_t states, int64_t rows, int dtype, int cplx, int time_varying, int64_t* out);
+int cplxamd_ssm_scan(const void* a_r, const void* a_i, const void* b_r, const void* b_i, const void* c_r, const void* c_i,
+                     const void* x_r, const void* x_i, const void* dt, const void* h_r, const void* h_i, void* y_r,
+                     void* y_i, void* f_r, void* f_i, const cplxamd_ssm_desc* d, int cplx, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
