@@ -261,6 +261,10 @@ SIGNATURES = {
     # SsmDesc, the plan fills SSM_PLAN_FIELDS int64)
     "cplxamd_ssm_plan": [_L, _L, _L, _I, _I, _I, _P],
     "cplxamd_ssm_scan": [_P] * 16 + [_I, _I, _P],
+    # still ABI 25: the fused parameter-gradient kernel behind cplx.ssm_scan's backward (csrc/ssm_grad.hip; the planes
+    # travel as two pointer arrays, the descriptor is SsmGradDesc, the plan fills SSM_PGRAD_PLAN_FIELDS int64)
+    "cplxamd_ssm_pgrad_plan": [_L, _L, _L, _I, _I, _I, _P],
+    "cplxamd_ssm_pgrad": [_P, _P, _P, _I, _I, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -351,6 +355,23 @@ class SsmDesc(ctypes.Structure):
 # the fields of cplxamd_ssm_plan's output (CPLXAMD_SSM_*) and the flag bits
 SSM_PLAN_FIELDS = ("chunk", "tile", "tiles", "group", "lds_bytes", "threads", "grid", "window")
 SSM_REVERSE, SSM_CONJ, SSM_LAG, SSM_DT_OUT = 1, 2, 4, 8
+
+
+class SsmGradDesc(ctypes.Structure):
+    """cplxamd_ssm_pgrad_desc: SsmDesc's fields with the gradients to form (`need`, SSM_NEED_*) and, in place of the
+    result's strides, those of the incoming gradient g; f_ns and f_stride are those of gf."""
+    _fields_ = [("n", c_int64), ("states", c_int64), ("a_es", c_int64), ("b_es", c_int64), ("c_es", c_int64),
+                ("a_ns", c_int64), ("b_ns", c_int64), ("c_ns", c_int64), ("h_ns", c_int64), ("f_ns", c_int64),
+                ("runs", ctypes.c_int32), ("flags", ctypes.c_int32), ("need", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("size", c_int64 * 3), ("a_stride", c_int64 * 3), ("b_stride", c_int64 * 3), ("c_stride", c_int64 * 3),
+                ("x_stride", c_int64 * 3), ("dt_stride", c_int64 * 3), ("h_stride", c_int64 * 3), ("g_stride", c_int64 * 3),
+                ("f_stride", c_int64 * 3)]
+
+
+# the fields of cplxamd_ssm_pgrad_plan's output (CPLXAMD_SSM_PGRAD_*), the bits of `need`, the planes of `in` and `out`
+SSM_PGRAD_PLAN_FIELDS = ("chunk", "tile", "tiles", "group", "lds_bytes", "ws_bytes", "threads", "grid")
+SSM_NEED_A, SSM_NEED_B, SSM_NEED_C, SSM_NEED_DT, SSM_NEED_X = 1, 2, 4, 8, 16
+SSM_PGRAD_IN, SSM_PGRAD_OUT = 15, 12
 
 
 class PfbDesc(ctypes.Structure):

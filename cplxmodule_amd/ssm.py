@@ -1,6 +1,7 @@
-"""The diagonal state-space scan with N states per channel, along the last dim, on the fused kernel of csrc/ssm.hip: the
-argument handling, the plan, the launch glue and the autograd Function behind cplx.ssm_scan, and the composed route
-(`composed`: torch products and cplx.linear_recurrence) that float64 takes and scripts/bench_ssm.py compares against.
+"""The diagonal state-space scan with N states per channel, along the last dim, on the fused kernels of csrc/ssm.hip and
+csrc/ssm_grad.hip: the argument handling, the plans, the launch glue and the autograd Function behind cplx.ssm_scan, and
+the composed route (`composed`: torch products and cplx.linear_recurrence) that float64 takes and scripts/bench_ssm.py
+compares against.
 
 One primitive (cplxamd_ssm_scan).  In processing order p = 0 .. T - 1 (step p is sample p, or T - 1 - p in reverse)
 
@@ -15,14 +16,17 @@ incoming gradients g of y and gf of the final state:
     dx[t] = dt[t] sum_n conj(b[n, t]) lambda[n, t]      -- the primitive on (a, c, b, g, dt, gf), all four flags flipped
     dh0[n] = conj(A[n, 0]) lambda[n, 0]                 -- lambda[., 0] is that call's final state
 
-so dx and dh0 cost one launch of the same kernel and nothing of size N T.  The parameter gradients are formed only when
-asked for, from h and lambda recomputed as [*B, N, T] tensors with the scan primitive (scan.run):
+so dx and dh0 cost one launch of the same kernel and nothing of size N T.  When a, b, c or dt require grad the backward is
+instead ONE launch of the parameter-gradient kernel (csrc/ssm_grad.hip: `run_grad`, `grad_plan`), which recomputes h and
+lambda in registers and writes dx, lambda[., 0] and
 
     dc = g conj(h),  db = lambda conj(X),  dA = lambda conj(h[p - 1]);   with dt:  da[n] = sum_t dA conj(dt A),
     ddt[t] = Re sum_n dA conj(a A) + Re(conj(x[t]) dX[t])
 
-torch products in the compute type, reduced with sum_to_size, rounded once: NOT the hot path, and they allocate the
-N T state inside the backward.  The backward is not differentiable: second derivatives are `composed`'s.
+per row of the batch in float32: [*B, N, T] where the operand varies along time, [*B, N, 1] (summed on chip) where it has
+one value per state.  The rows that share an operand are summed with sum_to_size and rounded once.  `parameter_gradients`
+states the same formulas with torch products on [*B, N, T] tensors; tests/test_ssm_host.py checks it against autograd and
+nothing else calls it.  The backward is not differentiable: second derivatives are `composed`'s.
 
 Leading dims broadcast by torch's rules and are read where they lie (stride 0 included) under _runs.py's rule of three
 batch runs, otherwise one copy.  Time must have stride 1 (or 0 in a, b, c): an operand whose time dim is strided is
@@ -102,6 +106,73 @@ def run(a, b, c, x, dt, h0, reverse=False, conj=False, lag=False, dt_out=False, 
     return yr, yi, fr, fi
 
 
+def grad_plan(T, N, rows=1, dtype=torch.float32, cplx=True, time_varying=True):
+    """The plan of the parameter-gradient kernel (csrc/ssm_grad.hip) for `rows` rows of `T` steps and `N` states -- a pure
+    host call like `plan`.  -> dict of _lib.SSM_PGRAD_PLAN_FIELDS: chunk, tile, tiles, group (the states per barrier), LDS
+    bytes, ws_bytes (the float32 states of h that enter the tiles, [rows, tiles, N], x 2 when complex; 0 for one tile),
+    threads, grid."""
+    out = (ctypes.c_int64 * len(_lib.SSM_PGRAD_PLAN_FIELDS))()
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise CplxAmdError(f"{FN}: no gradient plan in {dtype} (float32 or bfloat16; float64 takes ssm.composed)")
+    rc = _lib.load().cplxamd_ssm_pgrad_plan(int(T), int(N), int(rows), code(dtype), int(bool(cplx)), int(bool(time_varying)), out)
+    if rc == -3:
+        raise CplxAmdError(f"{FN}: {rows} rows of {T} steps exceed what the kernel indexes (2^40 steps, 2^31 - 1 rows)")
+    if rc < 0:
+        raise CplxAmdError(f"{FN}: no gradient plan for N = {N} states (1 .. {N_MAX})")
+    return dict(zip(_lib.SSM_PGRAD_PLAN_FIELDS, out))
+
+
+def run_grad(a, b, c, x, dt, h0, g, gf, reverse=False, cx=None, need=(True, True, True, True, True)):
+    """The gradients of the scan in ONE launch (cplxamd_ssm_pgrad), without autograd, on plane pairs laid out as `run`'s,
+    with g [*B, T] the gradient of y and gf [*B, N] (or (None, None)) that of the final state; `need` = (a, b, c, dt, x).
+    -> ((dxr, dxi), da, db, dc, ddt, (lr, li)): dx in the operands' dtype, everything else float32 and PER ROW of the
+    batch: da, db, dc plane pairs [*B, N, T] where the operand varies along time and [*B, N, 1] where it has one value per
+    state (summed over time on chip), ddt [*B, T], lambda[., 0] [*B, N]; None where `need` is off (the caller sums over
+    the rows that share an operand and rounds).  Nothing of size N T is allocated but a gradient of that shape."""
+    xr = x[0]
+    batch, T, N, dtype, dev = tuple(xr.shape[:-1]), xr.shape[-1], a[0].shape[-2], xr.dtype, xr.device
+    if cx is None:
+        cx = any(p[1] is not None for p in (a, b, c, x, h0, g, gf))
+    dense1 = lambda t: t if t is None or T == 1 or t.stride(-1) == 1 else t.contiguous()      # noqa: E731
+    # (an operand expanded along TIME has a gradient per step: it is copied, the kernel sums what has one value)
+    timed = lambda p: tuple(t if t is None or t.shape[-1] == 1 else dense1(t) for t in p)     # noqa: E731
+    f32 = lambda p: tuple(None if t is None else t.float() for t in p)                        # noqa: E731
+    named = [("a", timed(a)), ("b", timed(b)), ("c", timed(c)), ("x", tuple(dense1(t) for t in x)),
+             ("g", tuple(dense1(t) for t in g))] + [("dt", (dense1(dt), None))] * (dt is not None)
+    named += [("h", f32(h0))] * (h0[0] is not None) + [("f", f32(gf))] * (gf[0] is not None)
+    ops, rr = fit(batch + (T,), [p for _, p in named], dense(batch + (T,)),
+                  sorted(((k,) for k in range(len(named))), key=lambda k: named[k[0]][0] != "x"))
+    if len(rr) > MAX_RUNS:
+        raise CplxAmdError(f"{FN}: the batch dims do not fit {MAX_RUNS} runs")       # (every operand was copied: not reached)
+    got = {name: p for (name, _), p in zip(named, ops)}
+    none = (None, None)
+    (ar, ai), (br, bi), (cr, ci), (xr, xi), (gr, gi) = (got[k] for k in "abcxg")
+    dt, (hr, hi), (fr, fi) = got.get("dt", none)[0], got.get("h", none), got.get("f", none)
+    es = lambda t: 0 if t.shape[-1] == 1 else t.stride(-1)    # noqa: E731
+    wa, wb, wc, wd, wx = (bool(v) for v in need)
+    wd = wd and dt is not None
+    bits = ((_lib.SSM_NEED_A if wa else 0) | (_lib.SSM_NEED_B if wb else 0) | (_lib.SSM_NEED_C if wc else 0)
+            | (_lib.SSM_NEED_DT if wd else 0) | (_lib.SSM_NEED_X if wx else 0))
+    d = _lib.SsmGradDesc(n=T, states=N, a_es=es(ar), b_es=es(br), c_es=es(cr), a_ns=ar.stride(-2), b_ns=br.stride(-2),
+                         c_ns=cr.stride(-2), h_ns=0 if hr is None else hr.stride(-1), f_ns=0 if fr is None else fr.stride(-1),
+                         flags=_lib.SSM_REVERSE if reverse else 0, need=bits)
+    rows, _ = fill(d, rr, [name + "_stride" for name, _ in named])
+    new = lambda on, tail, kind=torch.float32: (tuple(torch.empty(batch + tail, dtype=kind, device=dev)       # noqa: E731
+                                                      if k == 0 or cx else None for k in range(2)) if on else none)
+    wide = lambda t: (N, T if es(t) == 1 else 1)              # noqa: E731
+    dx, da, db, dc = new(wx, (T,), dtype), new(wa, wide(ar)), new(wb, wide(br)), new(wc, wide(cr))
+    ddt, lam = new(wd, (T,))[0], new(True, (N,))
+    p = grad_plan(T, N, rows, dtype, cx, dt is not None or es(ar) == 1)
+    ws = torch.empty(p["ws_bytes"] // 4, dtype=torch.float32, device=dev) if p["ws_bytes"] else None
+    keep = lambda t: t if cx else None                        # noqa: E731
+    planes = lambda ts, count: (ctypes.c_void_p * count)(*(None if t is None else ptr(t).value for t in ts))   # noqa: E731
+    call("cplxamd_ssm_pgrad",
+         planes((ar, keep(ai), br, keep(bi), cr, keep(ci), xr, keep(xi), dt, hr, keep(hi), gr, keep(gi), fr, keep(fi)),
+                _lib.SSM_PGRAD_IN),
+         planes((*dx, *da, *db, *dc, ddt, *lam, ws), _lib.SSM_PGRAD_OUT), ctypes.byref(d), int(cx), code(dtype), stream_ptr())
+    return dx, da, db, dc, ddt, lam
+
+
 def _over(p, shape):
     return tuple(None if t is None else t.expand(shape) for t in p)
 
@@ -177,32 +248,32 @@ class _Ssm(torch.autograd.Function):
         dte = None if dt is None else dt.expand(batch + (T,))
         a, b, c = abc(ar, ai), abc(br, bi), abc(cr, ci)
         g, gf = (gr, gi if cx else None), (gfr, gfi if cx else None)
-        # dx and lambda[., 0]: the same kernel, b and c swapped, every flag flipped
-        dxr, dxi, lr, li = run(a, c, b, g, dte, gf, not reverse, True, True, True, cx)
-        ct = _ct(xr.dtype)
-        back = lambda t, like, part: (None if like is None else                                  # noqa: E731
-                                      (getattr(t, part) if t.is_complex() else t).sum_to_size(like.shape).to(like.dtype))
+        back = lambda t, like: None if t is None or like is None else t.sum_to_size(like.shape).to(like.dtype)   # noqa: E731
         grads = [None] * 11
-        grads[6], grads[7] = back(dxr, xr, "real"), None if xi is None or dxi is None else back(dxi, xi, "real")
-        at = T - 1 if reverse else 0
+        wants = (need[0] or need[1], need[2] or need[3], need[4] or need[5], need[8] and dt is not None)
+        if any(wants):
+            # every gradient from ONE launch of the parameter-gradient kernel, per row: the rows that share an operand
+            # are summed here, in float32, and rounded once
+            (dxr, dxi), da, db, dc, ddt, (lr, li) = run_grad(a, b, c, _over((xr, xi), batch + (T,)), dte,
+                                                             _over((hr, hi), batch + (N,)), g, gf, reverse, cx,
+                                                             wants + (need[6] or need[7],))
+            for k, (t, w) in enumerate(((da, wants[0]), (db, wants[1]), (dc, wants[2]))):
+                if w:
+                    grads[2 * k], grads[2 * k + 1] = back(t[0], ctx.saved_tensors[2 * k]), back(t[1], ctx.saved_tensors[2 * k + 1])
+            del da, db, dc
+            grads[8] = back(ddt, dt)
+        else:
+            # dx and lambda[., 0] alone: the scan kernel, b and c swapped, every flag flipped
+            dxr, dxi, lr, li = run(a, c, b, g, dte, gf, not reverse, True, True, True, cx)
+        grads[6], grads[7] = back(dxr, xr), back(dxi, xi)
         if need[9] or need[10]:
+            ct, at = _ct(xr.dtype), T - 1 if reverse else 0
             a0 = _z(tuple(None if t is None else t[..., at if t.shape[-1] > 1 else 0] for t in a), ct, cx)
             lam0 = _z((lr, li), ct, cx)
             if dt is not None:
                 a0 = torch.exp(dte[..., at].to(ct).unsqueeze(-1) * a0)
             dh = a0.conj() * lam0
-            grads[9], grads[10] = back(dh, hr, "real"), back(dh, hi, "imag")
-        if any(need[k] for k in (0, 1, 2, 3, 4, 5, 8)):
-            zz = lambda p: None if p[0] is None else _z(p, ct, cx)                               # noqa: E731
-            wants = (need[0] or need[1], need[2] or need[3], need[4] or need[5], need[8])
-            da, db, dc, ddt = parameter_gradients(zz(a), zz(b), zz(c), zz(_over((xr, xi), batch + (T,))),
-                                                  None if dt is None else dte.to(ct), zz(_over((hr, hi), batch + (N,))),
-                                                  zz(g), zz(gf), reverse, wants)
-            for k, (t, pr, pi) in enumerate(((da, ar, ai), (db, br, bi), (dc, cr, ci))):
-                if t is not None:
-                    grads[2 * k], grads[2 * k + 1] = back(t, pr, "real"), back(t, pi, "imag")
-            if ddt is not None:
-                grads[8] = back(ddt, dt, "real")
+            grads[9], grads[10] = back(dh.real, hr), back(dh.imag if cx else None, hi)
         return tuple(v if need[k] else None for k, v in enumerate(grads)) + (None,)
 
 

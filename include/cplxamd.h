@@ -1835,6 +1835,56 @@ int cplxamd_ssm_scan(const void* a_r, const void* a_i, const void* b_r, const vo
                      const void* x_r, const void* x_i, const void* dt, const void* h_r, const void* h_i, void* y_r,
                      void* y_i, void* f_r, void* f_i, const cplxamd_ssm_desc* d, int cplx, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * The gradients of a, b, c, dt and x of cplxamd_ssm_scan (REVERSE is the only flag it takes) in ONE launch that recomputes
+ * h and lambda in registers (csrc/ssm_grad.hip).  New exports under ABI 25: nothing existing changes.  With g the
+ * incoming gradient of y, gf that of the final state (NULL: zero), X = x or dt x, in processing order p:
+ *   lambda[s][p] = conj(c[s][p]) g[p] + conj(A[s][p + 1]) lambda[s][p + 1]      gf[s] enters step n - 1 unscaled
+ *   dc = g conj(h)   db = lambda conj(X)   dA = lambda conj(h[p - 1])   dX[p] = sum_s conj(b[s][p]) lambda[s][p]
+ *   dt NULL: da = dA, dx = dX.   dt given: da[s] = sum_p dA conj(dt A), dx = dt dX,
+ *                                ddt[p] = Re sum_s dA conj(a A) + Re(conj(x[p]) dX[p])
+ * `in`  (15 planes): a_r a_i b_r b_i c_r c_i x_r x_i dt h_r h_i g_r g_i gf_r gf_i -- laid out as cplxamd_ssm_scan's
+ *       (g as x, gf as h0; g_stride and f_stride are theirs); h0 and gf are float32 whatever the dtype.
+ * `out` (12 planes): dx_r dx_i (dtype, [rows][n], rounded once)  da_r da_i  db_r db_i  dc_r dc_i  ddt ([rows][n])
+ *       lam_r lam_i (lambda[s][0], [rows][states]; dL/dh0 = conj(A[.][0]) lambda[.][0])  ws -- all but dx float32.
+ * Every result is DENSE and PER ROW, rows in the order of the runs: the gradient of an operand that varies along time
+ * (a_es, b_es, c_es = 1) is [rows][states][n], that of an operand with one value per state [rows][states], summed over
+ * time on chip.  Rows that share an operand (stride 0) are the caller's to sum.  `need` (CPLXAMD_SSM_NEED_*) names the
+ * gradients to form; the planes of the others may be NULL, and so may lam_r / lam_i.  ws: WS_BYTES of the plan, read and
+ * written by the launch ([rows][tiles][states] float32 states of h, x 2 when complex); NULL when the plan says 0.
+ * A workgroup of 256 threads owns a row and walks its tiles last to first; with more than one tile a prologue in the same
+ * launch leaves the states of h that enter the tiles in ws.  The states go by in groups of GROUP with one barrier each.
+ * cplxamd_ssm_pgrad_plan is a pure function (no GPU).  Both check before any launch, as cplxamd_ssm_scan does:
+ * CPLXAMD_EINVAL also for a missing plane of a gradient in `need`, NEED_DT without dt, ws missing; CPLXAMD_ESHAPE.
+ * No atomics, no spin loops: reruns give the same bits.  Nothing is read on the host (capturable).
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_SSM_NEED_A = 1, CPLXAMD_SSM_NEED_B = 2, CPLXAMD_SSM_NEED_C = 4, CPLXAMD_SSM_NEED_DT = 8,
+       CPLXAMD_SSM_NEED_X = 16 };
+enum { CPLXAMD_SSM_PGRAD_CHUNK = 0,      /* steps per chunk (L): 16                                                     */
+       CPLXAMD_SSM_PGRAD_TILE,           /* steps per tile: 256 CHUNK                                                   */
+       CPLXAMD_SSM_PGRAD_TILES,          /* tiles per row                                                               */
+       CPLXAMD_SSM_PGRAD_GROUP,          /* states per barrier                                                          */
+       CPLXAMD_SSM_PGRAD_LDS_BYTES,
+       CPLXAMD_SSM_PGRAD_WS_BYTES,       /* 0 for one tile, else rows tiles states 4 (x 2 when complex)                 */
+       CPLXAMD_SSM_PGRAD_THREADS,
+       CPLXAMD_SSM_PGRAD_GRID,           /* rows                                                                        */
+       CPLXAMD_SSM_PGRAD_PLAN_FIELDS };
+typedef struct cplxamd_ssm_pgrad_desc {
+  int64_t n;              /* steps per row, >= 0 */
+  int64_t states;         /* 1 .. 256 */
+  int64_t a_es, b_es, c_es; /* element strides along time, 0 or 1 */
+  int64_t a_ns, b_ns, c_ns, h_ns, f_ns; /* element strides along the states (f: gf), >= 0 */
+  int32_t runs;           /* 0 .. 3 batch runs, run 0 outermost */
+  int32_t flags;          /* CPLXAMD_SSM_REVERSE or 0 */
+  int32_t need;           /* CPLXAMD_SSM_NEED_* */
+  int32_t reserved;       /* 0 */
+  int64_t size[3], a_stride[3], b_stride[3], c_stride[3], x_stride[3], dt_stride[3], h_stride[3], g_stride[3],
+      f_stride[3];
+} cplxamd_ssm_pgrad_desc; /* 312 bytes */
+int cplxamd_ssm_pgrad_plan(int64_t n, int64_t states, int64_t rows, int dtype, int cplx, int time_varying, int64_t* out);
+int cplxamd_ssm_pgrad(const void* const* in, void* const* out, const cplxamd_ssm_pgrad_desc* d, int cplx, int dtype,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
