@@ -265,6 +265,10 @@ SIGNATURES = {
     # travel as two pointer arrays, the descriptor is SsmGradDesc, the plan fills SSM_PGRAD_PLAN_FIELDS int64)
     "cplxamd_ssm_pgrad_plan": [_L, _L, _L, _I, _I, _I, _P],
     "cplxamd_ssm_pgrad": [_P, _P, _P, _I, _I, _P],
+    # still ABI 25: linear attention with a per-step decay behind cplx.linear_attention (csrc/linattn.hip; the descriptor
+    # is LinAttnDesc, the plan fills LINATTN_PLAN_FIELDS int64)
+    "cplxamd_linattn_plan": [_L, _L, _L, _L, _I, _P],
+    "cplxamd_linattn": [_P] * 15 + [_I, _P],
 }
 
 # modes of cplxamd_init_scale_store (CPLXAMD_INIT_SCALE_*)
@@ -372,6 +376,22 @@ class SsmGradDesc(ctypes.Structure):
 SSM_PGRAD_PLAN_FIELDS = ("chunk", "tile", "tiles", "group", "lds_bytes", "ws_bytes", "threads", "grid")
 SSM_NEED_A, SSM_NEED_B, SSM_NEED_C, SSM_NEED_DT, SSM_NEED_X = 1, 2, 4, 8, 16
 SSM_PGRAD_IN, SSM_PGRAD_OUT = 15, 12
+
+
+class LinAttnDesc(ctypes.Structure):
+    """cplxamd_linattn_desc: steps, head sizes (T, E, Ev), the step strides of q, k, v, o, the row strides of the states,
+    up to three batch runs (run 0 outermost) with the strides of q, k, v, lambda, the entering state, o and the final
+    state, the flags and the scale."""
+    _fields_ = [("T", c_int64), ("E", c_int64), ("Ev", c_int64), ("q_rs", c_int64), ("k_rs", c_int64), ("v_rs", c_int64),
+                ("o_rs", c_int64), ("s_rs", c_int64), ("f_rs", c_int64), ("runs", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("size", c_int64 * 3), ("q_stride", c_int64 * 3), ("k_stride", c_int64 * 3), ("v_stride", c_int64 * 3),
+                ("l_stride", c_int64 * 3), ("s_stride", c_int64 * 3), ("o_stride", c_int64 * 3), ("f_stride", c_int64 * 3),
+                ("scale", c_double)]
+
+
+# the fields of cplxamd_linattn_plan's output (CPLXAMD_LINATTN_*) and the flag bits
+LINATTN_PLAN_FIELDS = ("chunk", "head_e", "head_v", "slice", "slices", "chunks", "grid", "lds_bytes", "threads")
+LINATTN_REVERSE, LINATTN_CONJ, LINATTN_LAG, LINATTN_SCALE_IN = 1, 2, 4, 8
 
 
 class PfbDesc(ctypes.Structure):

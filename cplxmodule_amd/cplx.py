@@ -1154,6 +1154,34 @@ def ssm_scan(a, b, c, x, dt=None, h0=None, return_state=False, reverse=False):
     return _ssm.ssm_scan(a, b, c, x, dt, h0, return_state, reverse)
 
 
+# ---- linear attention with a per-step decay: the recurrence whose state is a matrix, on a chunked MFMA kernel
+# (cplxmodule_amd/linear_attention.py, csrc/linattn.hip) -----------------------------------------------------------------
+def linear_attention(query, key, value, log_decay=None, state=None, return_state=False, scale=None, reverse=False):
+    r"""Linear attention with a decay per step -- retention, gated linear attention, the "SSD" recurrence -- of `Cplx`
+    tensors query, key [..., T, E] and value [..., T, Ev] -> [..., T, Ev]: O(T), with an E x Ev complex state per batch entry.
+
+        S[t] = exp(lambda[t]) S[t - 1] + k[t]^H (x) v[t],   o[t] = scale q[t] S[t],   S[-1] = `state` (default 0)
+        o[t] = scale sum_{s <= t} exp(Lambda[t] - Lambda[s]) (q[t] k[s]^H) v[s],   Lambda = the running sum of lambda
+
+    `log_decay` (lambda) is None (every weight exactly 1), a real tensor or a `Cplx` (retention's gamma e^{i theta} is
+    log gamma + i theta), [..., T] with leading dims broadcastable to the batch.  Contract: Re lambda <= 0; then every
+    exponent the kernel forms has a non-positive real part.  Re lambda > 0 is not special-cased: a weight can overflow
+    where the sequential value is finite.  `state` is a `Cplx` [..., E, Ev]; with `return_state=True` the result is (o, S)
+    with S the state after the last processed step: passed as `state` of the next block it continues the row.  `scale`
+    defaults to 1 / sqrt(E); `reverse=True` runs t = T - 1 .. 0.  1 <= E, Ev <= 128; the leading dims of query, key and
+    value are equal (no broadcasting) and are read in place through strides: a [B, T, H, E] projection viewed as
+    [B, H, T, E] is not copied, and the result follows the query's memory order.
+    float32 and bfloat16 run ONE launch: a workgroup owns a batch entry and 32 value columns and walks the
+    row in chunks of 32 steps whose products run on the float32 matrix instruction (bf16 operands are widened on chip;
+    arithmetic and state are float32, o and S are rounded once).  float64 takes `linear_attention.composed`, the
+    quadratic masked form, which is also what differentiates to any order.  Empty T or batch: no launch.
+    Gradients: dq, dk, dv and dstate are the same kernel with the roles swapped (three launches at most; one that is not
+    asked for is not launched); dlog_decay is two row sums and a running sum of them.  Differentiable once.  Rows are
+    not cut across workgroups: a few long rows run on a few workgroups."""
+    from . import linear_attention as _linear_attention
+    return _linear_attention.linear_attention(query, key, value, log_decay, state, return_state, scale, reverse)
+
+
 def cumsum(x, reverse=False):
     r"""The running sum along the last dim of a `Cplx` or a real tensor, on `linear_recurrence`'s kernel with a = 1 (a
     stride-0 view: no plane of ones).  Operands, layouts, dtypes and derivatives as `linear_recurrence`."""

@@ -1885,6 +1885,61 @@ int cplxamd_ssm_pgrad_plan(int64_t n, int64_t states, int64_t rows, int dtype, i
 int cplxamd_ssm_pgrad(const void* const* in, void* const* out, const cplxamd_ssm_pgrad_desc* d, int cplx, int dtype,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Linear attention with a per-step complex decay: the recurrence whose state is a matrix (cplx.linear_attention;
+ * csrc/linattn.hip).  New exports under ABI 25: nothing existing changes.  For every batch entry, in processing order
+ * p = 0 .. T - 1 (step p is row p, or row T - 1 - p with CPLXAMD_LINATTN_REVERSE), with S an E x Ev complex matrix:
+ *   S[p] = exp(mu[p]) S[p - 1] + k[p]^H (x) v[p],   o[p] = scale q[p] S[p],   S[-1] = s (zero when s_r is NULL)
+ *   f = S[T - 1]  (written when f_r is given)
+ * mu[p] = lambda[p]; its conjugate with CPLXAMD_LINATTN_CONJ; with CPLXAMD_LINATTN_LAG the lambda of step p - 1, and
+ * step 0 has none: s enters it unscaled and no address outside lambda is formed.  With CPLXAMD_LINATTN_SCALE_IN the
+ * factor `scale` moves from the output to the update: S[p] = exp(mu[p]) S[p - 1] + scale k[p]^H (x) v[p], o[p] = q[p] S[p].
+ * l_r NULL: every weight is 1 and the instance that runs holds no exponential; l_i NULL: a real decay.
+ * THE ADJOINT: with g the incoming gradient of o and gf that of f (autograd's convention), every data gradient is the
+ * same call with the roles swapped (X^H: the conjugate transpose of a state):
+ *   dq = run(g, v, k, s^H; CONJ)   dk = run(v, g, q, gf^H; flipped REVERSE, LAG, SCALE_IN)
+ *   dv = run(k, q, g, gf; flipped REVERSE, LAG, CONJ, SCALE_IN),  ds = conj(exp lambda[first]) (final state of the dv call)
+ * Row t of batch entry r = (i0, i1, i2) of q lies at q_r / q_i [sum_j i_j q_stride[j] + t q_rs + e]; k, v and o
+ * likewise (features have stride 1); lambda at l_r / l_i [sum_j i_j l_stride[j] + t]; s and f at
+ * [sum_j i_j *_stride[j] + e *_rs + ev].  Strides are in elements; those of q, k, v, lambda and s may be 0.  dtype (of
+ * the planes of q, k, v and o): F32 or BF16.  lambda, s and f are float32 planes whatever the dtype: the state is never
+ * rounded, neither between chunks nor on the way out (the adjoint's final state is a factor of a gradient).
+ * A workgroup of 256 threads owns one batch entry and SLICE columns of v, and walks the row in chunks of CHUNK steps:
+ * inside a chunk every product (q k^H, its weighted form times v, q S, k^H v) runs on v_mfma_f32_32x32x2_f32 (bf16
+ * operands are widened when they enter LDS); S stays in LDS as float32 from chunk to chunk.  Every exponent is a
+ * difference of two in-chunk prefix sums of mu (kept in float64, rounded once), so for Re lambda <= 0 none has a
+ * positive real part.  1 <= E, Ev <= 128.  Rows are not cut across workgroups.
+ * cplxamd_linattn_plan is a pure function (no GPU).  Both check before any launch: CPLXAMD_EINVAL (a NULL plane that is
+ * required, l_i without l_r, s_i without s_r or the reverse, likewise f, dtype, E or Ev outside 1 .. 128, unknown
+ * flags, negative sizes or strides, o_rs below Ev, a scale that is not finite), CPLXAMD_ESHAPE (T above 2^31 - 64, more
+ * than 2^31 - 1 workgroups).  No batch entries or T = 0: returns 0.  No atomics, no spin loops, no workspace: reruns
+ * give the same bits.  Nothing is read on the host (capturable).
+ * ---------------------------------------------------------------------------------- */
+enum { CPLXAMD_LINATTN_REVERSE = 1, CPLXAMD_LINATTN_CONJ = 2, CPLXAMD_LINATTN_LAG = 4, CPLXAMD_LINATTN_SCALE_IN = 8 };
+enum { CPLXAMD_LINATTN_CHUNK = 0,        /* steps per chunk (C): 32                                                     */
+       CPLXAMD_LINATTN_HEAD_E,           /* the compiled head E rounds up to: 32, 64 or 128                             */
+       CPLXAMD_LINATTN_HEAD_V,           /* Ev rounded up to whole slices                                               */
+       CPLXAMD_LINATTN_SLICE,            /* value columns per workgroup: 32                                             */
+       CPLXAMD_LINATTN_SLICES,           /* ceil(Ev / slice): the workgroups that recompute q k^H of one batch entry    */
+       CPLXAMD_LINATTN_CHUNKS,           /* ceil(T / chunk)                                                             */
+       CPLXAMD_LINATTN_GRID,             /* batch x slices                                                              */
+       CPLXAMD_LINATTN_LDS_BYTES,
+       CPLXAMD_LINATTN_THREADS,
+       CPLXAMD_LINATTN_PLAN_FIELDS };
+typedef struct cplxamd_linattn_desc {
+  int64_t T, E, Ev;       /* steps per row (>= 0), features of q and k, features of v: 1 .. 128 */
+  int64_t q_rs, k_rs, v_rs, o_rs; /* element strides from step to step */
+  int64_t s_rs, f_rs;     /* element strides from row to row of the states s and f */
+  int32_t runs;           /* 0 .. 3 batch runs, run 0 outermost */
+  int32_t flags;          /* CPLXAMD_LINATTN_* bits */
+  int64_t size[3], q_stride[3], k_stride[3], v_stride[3], l_stride[3], s_stride[3], o_stride[3], f_stride[3];
+  double scale;
+} cplxamd_linattn_desc;   /* 280 bytes */
+int cplxamd_linattn_plan(int64_t T, int64_t E, int64_t Ev, int64_t batch, int dtype, int64_t* plan);
+int cplxamd_linattn(const void* q_r, const void* q_i, const void* k_r, const void* k_i, const void* v_r, const void* v_i,
+                    const float* l_r, const float* l_i, const float* s_r, const float* s_i, void* o_r, void* o_i,
+                    float* f_r, float* f_i, const cplxamd_linattn_desc* d, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
